@@ -13,8 +13,16 @@ store B, C, D; dead temps stay in registers — the live_gids rule,
 reference ramba/ramba.py:8123).
 
 Run:  python bench.py [--gpus N] [--steps K] [--warmup W] [--elems E]
+                      [--dump-outputs DIR] [--full]
 Multi-GPU (driver contract): torchrun --nproc-per-node N bench.py --gpus N
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line.
+--dump-outputs DIR also writes what the last timed step returned as
+DIR/<name>.npy (a fixed sample of the larger arrays; see sample_output).
+--full adds the legs that need runs of their own: the per-kernel roofline
+figures (`roofline`) and the CPU baselines (`cpu_baseline`); both are
+null in the line of a plain run.
 """
 
 import argparse
@@ -28,6 +36,39 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_BYTES = 8.0e12          # MI355X HBM3E spec peak
+DUMP_MAX_BYTES = 48_000_000      # --dump-outputs budget over all arrays
+DUMP_SEED = 20240607             # fixes which elements a sample holds
+
+
+def sample_output(x, max_bytes, rng):
+    """Host copy of `x` (a ramba_amd array or a scalar) for --dump-outputs.
+
+    An array of at most `max_bytes` is returned whole.  A larger one is
+    sampled along axis 0, the same elements on every run with the same
+    `rng` state: its first and last rows (where tail handling lives) plus
+    every stride-th row from an `rng`-drawn offset, concatenated in that
+    order.  The rows are compacted by the engine, so only the sample
+    crosses to the host."""
+    import numpy as np
+    if not hasattr(x, "asarray"):
+        return np.asarray(x, dtype=np.float64)
+    if x.ndim == 0 or x.size * x.dtype.itemsize <= max_bytes:
+        out = x.asarray()
+    else:
+        n0 = x.shape[0]
+        row_bytes = x.size // n0 * x.dtype.itemsize
+        max_rows = max_bytes // row_bytes
+        if max_rows < 3:
+            raise ValueError(f"one row of shape {x.shape} exceeds the "
+                             f"{max_bytes} B sample budget")
+        edge = max(1, min(65536, max_rows // 8))
+        stride = -(-n0 // (max_rows - 2 * edge))
+        off = int(rng.integers(stride))
+        out = np.concatenate([part.copy().asarray() for part in
+                              (x[:edge], x[off::stride], x[n0 - edge:])])
+    if out.dtype not in (np.float32, np.float64):
+        out = out.astype(np.float64)
+    return out
 
 
 def main():
@@ -47,13 +88,18 @@ def main():
                          "mixed = configs[4] 8192^2 fp64 "
                          "iota→sin→stencil→sum pipeline")
     ap.add_argument("--stencil-n", type=int, default=4096)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as "
+                         "DIR/<name>.npy (large arrays as a fixed sample)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the roofline and cpu_baseline legs")
     args = ap.parse_args()
     if args.steps is None:
         # short pipelines need more steps so the one-time allocator-growth
         # and first-compile spikes stay out of the steady-state window
         # windows sized so the box's occasional random 20-40 ms stall
         # (observed ~once per run at arbitrary steps, not attributable to
-        # GC or our code — gpurun_out/st2.log attribution test) cannot
+        # GC or our code in a per-step attribution test) cannot
         # dominate a short window or always land inside a long one
         args.steps = {"flagship": 5, "reduce": 8, "stencil": 12,
                       "mixed": 20}[args.workload]
@@ -105,6 +151,7 @@ def main():
             D = B * B + C ** 2
             ra.sync()
             return B, C, D
+        out_names = ("B", "C", "D")
         metric = ("GElem/s, 1e9-elem fused sin²+cos² fp64 "
                   "(BASELINE configs[1])")
         wl_desc = ("1e9-elem fp64 arange→sin²+cos², one shard per GPU, "
@@ -121,6 +168,7 @@ def main():
             s = A.sum()
             assert abs(float(s) - N) < 1e-3 * N
             return s
+        out_names = ("sum",)
         metric = ("GElem/s, 1e9-elem fp64 global sum via RCCL allreduce "
                   "(BASELINE configs[2])")
         wl_desc = "1e9-elem fp64 sum(), 8 B/elem read + one 8 B allreduce"
@@ -161,6 +209,7 @@ def main():
             # escape the timed region (host-side flush happens after the
             # barrier) and triggers the WAR temp-dance on A every step.
             return float(A.sum())
+        out_names = ("sum",)
         metric = ("GElem/s, 8192^2 fp64 iota→sin→stencil→sum pipeline "
                   "(BASELINE configs[4])")
         wl_desc = ("8192^2 fp64: iota+sin+stencil+sum in ONE fused "
@@ -183,6 +232,7 @@ def main():
             bufs.reverse()
             ra.sync()
             return dst
+        out_names = ("out",)
         metric = (f"GElem/s, {S}x{S} fp32 5-pt Laplacian stencil "
                   "(BASELINE configs[3])")
         wl_desc = (f"{S}^2 fp32 5-point stencil, 2-D blocks + halo "
@@ -192,7 +242,7 @@ def main():
     keep = None
     # the box exhibits ONE ~36 ms runtime stall per process, 3-5 s after
     # start (observed at arbitrary step indices; independent of GC and of
-    # our kernels — gpurun_out/s1err.log).  Warm up for at least 6 s of
+    # our kernels in per-step traces).  Warm up for at least 6 s of
     # wall time so it lands before the timed window; the JSON reports the
     # warmup steps actually done.
     warm_requested = args.warmup
@@ -252,11 +302,27 @@ def main():
     ms_per_step = elapsed / args.steps * 1000.0
     value = N * args.steps / elapsed / 1e9     # GElem/s, whole job
 
-    # ---- roofline leg: HIP-event time of the fused kernel itself ----------
-    backend.time_kernels = True
+    # ---- --dump-outputs: what the last timed step handed its caller -------
+    if args.dump_outputs:
+        outs = keep if isinstance(keep, tuple) else (keep,)
+        outs = dict(zip(out_names, outs))
+        if args.workload == "mixed":
+            outs["A"] = A        # the step's array result (written in place)
+        rng = np.random.default_rng(DUMP_SEED)
+        if rank == 0:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, x in outs.items():
+            # collective for N>1 (asarray gathers), so every rank samples
+            host = sample_output(x, DUMP_MAX_BYTES // len(outs), rng)
+            if rank == 0:
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), host)
+        del outs, x, host
+
+    # ---- roofline leg (--full): HIP-event time of the fused kernel itself -
+    backend.time_kernels = args.full
     backend.kernel_times_ms = []
     backend.kernel_keys = []
-    for _ in range(3):
+    for _ in range(3 if args.full else 0):
         keep = step()
     backend.time_kernels = False
     local_elems = 0
@@ -326,9 +392,9 @@ def main():
             # unit over the fused execution time) is reported alongside
             roofline["equiv_unfused_frac"] =                 32 * local_elems / (kms / 1e3) / HBM_PEAK_BYTES
 
-    # ---- cpu_baseline leg (rank 0, N=1 only): oracle/fused_cpu.c ----------
+    # ---- cpu_baseline leg (--full; rank 0, N=1 only): oracle/fused_cpu.c --
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline \
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline \
             and args.workload == "flagship":
         exe = os.path.join(ROOT, "oracle", "_build", "fused_cpu")
         if os.path.exists(exe):
