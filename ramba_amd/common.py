@@ -12,6 +12,8 @@ Env knobs (analog of ramba/common.py:26-235):
   RAMBA_DEBUG          - debug print level
   RAMBA_BORDER         - default shard border ring width (elements), default 4
   RAMBA_TIMING         - timing summary level
+  RAMBA_REMAT          - rematerialise index-pure arrays instead of reading them
+  RAMBA_REMAT_MIN_BYTES - smallest per-rank shard that is rematerialised
 """
 
 import functools
@@ -37,6 +39,21 @@ overlap_exchange = int(os.environ.get("RAMBA_OVERLAP", "1"))
 # and the pair fuses into one LDS-tiled kernel on the HIP backend; 0
 # restores the reference's flush-at-alias behaviour (ramba.py:8434-8443)
 stage_fusion = int(os.environ.get("RAMBA_STAGE_FUSION", "1"))
+# index-pure rematerialisation ACROSS flushes: an array whose whole content
+# is a cheap pure function of the global index (arange/linspace/fromfunction/
+# constant fills) keeps that recipe on its bdarray; a later group reading it
+# recomputes the value from the index instead of loading it (8 B/elem of HBM
+# buys far more VALU work than such a recipe costs).  0 restores plain
+# memory reads.  Both are module attributes so tests can flip them in-process.
+remat = int(os.environ.get("RAMBA_REMAT", "1"))
+# substitute only when the largest per-rank shard is at least this big: a
+# smaller array can be re-read from the 256 MiB Infinity Cache, so the
+# saving is small (and small test inputs keep exercising the load paths)
+remat_min_bytes = int(os.environ.get("RAMBA_REMAT_MIN_BYTES",
+                                     str(256 << 20)))
+# debug counter: reads served by rematerialisation since import (tests
+# assert on it so that they cannot pass vacuously)
+remat_substitutions = 0
 
 
 def dprint(level, *args):

@@ -13,7 +13,7 @@ import numbers
 
 import numpy as np
 
-from . import ir
+from . import common, ir
 from .common import dprint
 from .shardview import exec_boxes, exec_boxes_eq
 
@@ -36,7 +36,7 @@ class bdarray:
     deferred-delete path of ramba.py:8321-8328)."""
 
     __slots__ = ("gid", "shape", "dtype", "divisions", "border", "constructed",
-                 "nviews", "flex", "__weakref__")
+                 "nviews", "flex", "pure", "__weakref__")
 
     def __init__(self, shape, dtype, divisions, border, flex=True):
         self.gid = next_gid()
@@ -51,6 +51,10 @@ class bdarray:
         # ramba/ramba.py:8093-8101 "Change distributions for any flexible
         # arrays")
         self.flex = flex
+        # PureRecipe while the whole content is a known cheap function of
+        # the global index (set after a group executes, cleared by ANY
+        # write registration); None otherwise
+        self.pure = None
 
     @property
     def is_flex(self):
@@ -123,6 +127,9 @@ class FusedGroup:
         # sub-box of A: fused into the tiled kernel (interior partials)
         # + a tiny complement reduce (runtime/staged_exec)
         self.staged_reductions = [] # [(src ndarray, written_view, pend)]
+        # rematerialised reads: (PureRecipe, view) -> instantiated expr, so
+        # repeated reads share ONE tree (sin(A)/cos(A) still pair up)
+        self._remat = {}
 
     # -- naming -------------------------------------------------------------
 
@@ -160,7 +167,12 @@ class FusedGroup:
         must merge into ONE var, or the kernel's SSA forwarding loses the
         in-group RAW (caught by fuzz seed 39 on the HIP path — the CPU
         oracle's sequential memory interpretation hides it)."""
-        gid = arr.bdarray.gid
+        bd = arr.bdarray
+        gid = bd.gid
+        if written:
+            # every fused-group write (and register_empty) lands here:
+            # the content stops being the recorded function of the index
+            bd.pure = None
         key = (gid, arr.view)
         name = self._var_by_key.get(key)
         if name is not None:
@@ -187,6 +199,11 @@ class FusedGroup:
             dt = np.asarray(value).dtype
         self.scalars[name] = (value, dt)
         return name, dt
+
+    def scalar_typed(self, value, dt):
+        name = self.fresh("s")
+        self.scalars[name] = (value, dt)
+        return name
 
 
 # ---------------------------------------------------------------------------
@@ -264,8 +281,13 @@ def _subst(group, tree, reads_out):
     if _is_ndarray(tree):
         if tree.shape == ():
             raise NotImplementedError("0-d distributed arrays")
+        bd = tree.bdarray
+        if bd.pure is not None:
+            e = _remat_read(group, tree)
+            if e is not None:
+                return e
         name = group.arr_var(tree, written=False)
-        reads_out.append((tree.bdarray.gid, tree.view))
+        reads_out.append((bd.gid, tree.view))
         return ir.Ref(name, tree.dtype)
     if isinstance(tree, (numbers.Number, np.bool_, np.number)):
         name, dt = group.scalar_var(tree)
@@ -287,6 +309,209 @@ def _subst(group, tree, reads_out):
     if isinstance(tree, (ir.Ref, ir.ScalarArg)):
         return tree
     raise TypeError(f"bad expr leaf {tree!r}")
+
+
+# ---------------------------------------------------------------------------
+# index-pure rematerialisation across flushes (common.remat)
+# ---------------------------------------------------------------------------
+
+REMAT_MAX_NODES = 12
+_REMAT_BIN = frozenset(("add", "sub", "mul", "minimum", "maximum",
+                        "gt", "lt", "ge", "le", "eq", "ne"))
+_REMAT_UN = frozenset(("neg", "abs"))
+
+
+class PureRecipe:
+    """The content of a whole backing array as a function of its global
+    index: `tree` has only Iota / Const / ScalarArg leaves (Iota(d) = base
+    coordinate d) and `scalars` binds the ScalarArg VALUES.  `nbytes` is the
+    largest per-rank shard (replicated state, so every rank decides alike);
+    `composed` caches the tree composed with each read view."""
+
+    __slots__ = ("tree", "scalars", "nbytes", "composed")
+
+    def __init__(self, tree, scalars, nbytes):
+        self.tree = tree
+        self.scalars = scalars      # name -> (value, dtype)
+        self.nbytes = nbytes
+        self.composed = {}          # View -> (template, values) | None
+
+
+def _inline_pure(e, env, count, names):
+    """`e` with in-group refs inlined, or None if it is not a cheap pure
+    function of the index.  A statement already carries the cast to its
+    target's dtype, so inlining a ref keeps every intermediate rounding."""
+    if isinstance(e, ir.Ref):
+        ent = env.get(e.name)
+        if ent is None:
+            return None
+        count[0] += ent[1]
+        for n in ent[2]:
+            if n not in names:
+                names.append(n)
+        return ent[0]
+    count[0] += 1
+    if isinstance(e, (ir.Iota, ir.Const)):
+        return e
+    if isinstance(e, ir.ScalarArg):
+        if e.name not in names:
+            names.append(e.name)
+        return e
+    if isinstance(e, ir.Bin):
+        if e.op not in _REMAT_BIN:
+            return None
+        a = _inline_pure(e.a, env, count, names)
+        b = _inline_pure(e.b, env, count, names) if a is not None else None
+        return None if b is None else ir.Bin(e.op, a, b, e.dtype)
+    if isinstance(e, ir.Un):
+        if e.op not in _REMAT_UN:
+            return None
+        a = _inline_pure(e.a, env, count, names)
+        return None if a is None else ir.Un(e.op, a, e.dtype)
+    if isinstance(e, ir.Cast):
+        a = _inline_pure(e.a, env, count, names)
+        return None if a is None else ir.Cast(a, e.dtype)
+    if isinstance(e, ir.Where):
+        c = _inline_pure(e.c, env, count, names)
+        a = _inline_pure(e.a, env, count, names) if c is not None else None
+        b = _inline_pure(e.b, env, count, names) if a is not None else None
+        return None if b is None else ir.Where(c, a, b, e.dtype)
+    return None
+
+
+def pure_targets(group, live):
+    """[(var, inlined tree, scalar names)] for the live arrays this group
+    leaves holding a cheap pure function of the index: assigned once,
+    through the identity view over the whole array.  Depends only on the
+    group's structure, so the runtime caches it with the execution recipe."""
+    env = {}
+    nassign = {}
+    for st in group.statements:
+        nassign[st.target] = nassign.get(st.target, 0) + 1
+        count, names = [0], []
+        t = _inline_pure(st.expr, env, count, names)
+        env[st.target] = None if t is None else (t, count[0], tuple(names))
+    out = []
+    for name, oi in live.items():
+        ent = env.get(name)
+        if ent is None or ent[1] > REMAT_MAX_NODES or nassign[name] != 1:
+            continue
+        if not oi.view.is_identity_for(oi.bd.shape):
+            continue
+        out.append((name, ent[0], ent[2]))
+    return out
+
+
+def record_pure(group, live, targets):
+    """Bind the scalar values of `targets` and store the recipes (called
+    after the group executed)."""
+    for name, tree, names in targets:
+        bd = live[name].bd
+        # exactly one write registration (an `empty` + assign pair is two)
+        if sum(1 for (g, _) in group.write_views if g == bd.gid) != 1:
+            continue
+        d = bd.divisions
+        ext = np.maximum(d[:, 1, :] - d[:, 0, :] + 1, 0)
+        nbytes = int(ext.prod(axis=1).max()) * bd.dtype.itemsize
+        bd.pure = PureRecipe(tree, {n: group.scalars[n] for n in names},
+                             nbytes)
+
+
+def _compose(pr, view):
+    """(template, values): pr.tree read through `view`, with Iota(d)
+    replaced by offset + step * Iota(view axis) and every scalar (the
+    recipe's own and the view's) a placeholder ScalarArg '@k' whose value
+    is values[k] — kernel keys stay independent of the values."""
+    nb = view.base_ndim
+    vals = []
+
+    def ph(value, dt):
+        vals.append((value, dt))
+        return ir.ScalarArg(f"@{len(vals) - 1}", dt)
+
+    rep = None
+    ident = (view.axis_map == tuple(range(nb)) and len(view.shape) == nb
+             and all(s == 1 for s in view.steps)
+             and not any(view.offset))
+    if not ident:
+        rep = {}
+        for d in range(nb):
+            axes = [v for v in range(view.ndim)
+                    if view.axis_map[v] == d and view.steps[v] != 0]
+            if len(axes) > 1:
+                return None         # not an affine map of distinct axes
+            e = ph(int(view.offset[d]), ir.I64)
+            if axes:
+                e = ir.Bin("add", e,
+                           ir.Bin("mul", ph(int(view.steps[axes[0]]), ir.I64),
+                                  ir.Iota(axes[0]), ir.I64), ir.I64)
+            rep[d] = e
+    smap = {n: ph(v, dt) for n, (v, dt) in pr.scalars.items()}
+
+    def walk(e):
+        if isinstance(e, ir.Iota):
+            return e if rep is None else rep[e.axis]
+        if isinstance(e, ir.ScalarArg):
+            return smap[e.name]
+        if isinstance(e, ir.Bin):
+            return ir.Bin(e.op, walk(e.a), walk(e.b), e.dtype)
+        if isinstance(e, ir.Un):
+            return ir.Un(e.op, walk(e.a), e.dtype)
+        if isinstance(e, ir.Cast):
+            return ir.Cast(walk(e.a), e.dtype)
+        if isinstance(e, ir.Where):
+            return ir.Where(walk(e.c), walk(e.a), walk(e.b), e.dtype)
+        return e
+
+    return walk(pr.tree), vals
+
+
+def _remat_template(arr):
+    """The composed recipe for reading `arr`, or None to read memory.
+    Uses replicated state only, so every rank takes the same branch."""
+    pr = arr.bdarray.pure
+    if not common.remat or pr.nbytes < common.remat_min_bytes:
+        return None
+    view = arr.view
+    try:
+        return pr.composed[view]
+    except KeyError:
+        if len(pr.composed) > 256:
+            pr.composed.clear()
+        comp = pr.composed[view] = _compose(pr, view)
+        return comp
+
+
+def _instantiate(e, names):
+    if isinstance(e, ir.ScalarArg):
+        return ir.ScalarArg(names[int(e.name[1:])], e.dtype)
+    if isinstance(e, ir.Bin):
+        return ir.Bin(e.op, _instantiate(e.a, names),
+                      _instantiate(e.b, names), e.dtype)
+    if isinstance(e, ir.Un):
+        return ir.Un(e.op, _instantiate(e.a, names), e.dtype)
+    if isinstance(e, ir.Cast):
+        return ir.Cast(_instantiate(e.a, names), e.dtype)
+    if isinstance(e, ir.Where):
+        return ir.Where(_instantiate(e.c, names), _instantiate(e.a, names),
+                        _instantiate(e.b, names), e.dtype)
+    return e
+
+
+def _remat_read(group, arr):
+    """Expression recomputing `arr` from the index (no array var, nothing
+    added to read_views: no load, no halo, no WAR hazard), or None."""
+    comp = _remat_template(arr)
+    if comp is None:
+        return None
+    key = (arr.bdarray.pure, arr.view)
+    e = group._remat.get(key)
+    if e is None:
+        tmpl, vals = comp
+        names = [group.scalar_typed(v, dt) for (v, dt) in vals]
+        e = group._remat[key] = _instantiate(tmpl, names)
+    common.remat_substitutions += 1
+    return e
 
 
 def _tree_ndarrays(tree, out):
@@ -449,8 +674,12 @@ def add_op(write_arr, assign_op, rhs_tree, empty_like=None):
     # version of something read (in this op or earlier in the group) ->
     # compute into a temp, flush, then assign temp to target.
     if write_arr is not None:
+        # (a rematerialised operand is never loaded, so it cannot conflict)
         conflict = any(o.bdarray.gid == write_arr.bdarray.gid
-                       and o.view != write_arr.view for o in operands)
+                       and o.view != write_arr.view
+                       and (o.bdarray.pure is None
+                            or _remat_template(o) is None)
+                       for o in operands)
         g = _state["group"]
         if not conflict and g is not None:
             conflict = any(rgid == write_arr.bdarray.gid and

@@ -9,10 +9,12 @@ extension or a GPU is missing — no CPU fallback exists in the product path.
 
 import ctypes
 import os
+import time as _time
 
 import numpy as np
 
-from . import codegen
+from . import codegen, common
+from .common import add_time
 from .shardview import box_shape
 
 LIBPATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_lib",
@@ -374,8 +376,7 @@ class HipBackend:
         return gk
 
     def launch(self, plan, recipe=None):
-        from .common import ntiming, add_time
-        import time as _time
+        ntiming = common.ntiming
         _t0 = _time.perf_counter() if ntiming else 0.0
         if recipe is not None and recipe.backend_kernel is not None:
             gk = recipe.backend_kernel

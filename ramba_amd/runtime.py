@@ -22,7 +22,7 @@ import time
 
 import numpy as np
 
-from . import deferred, ir
+from . import common, deferred, ir
 from .common import add_time, default_border, default_divisions
 from .shardview import (box_contains, box_intersect, box_shape,
                         box_subtract)
@@ -72,7 +72,7 @@ class Recipe:
     """Cached execution geometry for one fused-group structure."""
     __slots__ = ("plan", "temp_specs", "comm_msgs", "temp_geom",
                  "adopted_divs", "backend_kernel", "units",
-                 "pre_wait_units")
+                 "pre_wait_units", "pure_targets")
 
     def __init__(self):
         self.plan = None
@@ -87,6 +87,8 @@ class Recipe:
         # `pre_wait_units` of them run between comms-post and comms-wait
         self.units = None
         self.pre_wait_units = 0
+        # deferred.pure_targets of the group structure (None = not analysed)
+        self.pure_targets = None
 
 
 class Runtime:
@@ -205,7 +207,7 @@ class Runtime:
             add_time("run_deferred_ops", time.perf_counter() - t0)
 
     def _execute_group(self, group):
-        from .common import ntiming
+        ntiming = common.ntiming
         t0 = time.perf_counter() if ntiming else 0.0
         live, dead = deferred.compute_live_vars(group)
         cache = getattr(self, "_recipe_cache", None)
@@ -220,12 +222,28 @@ class Runtime:
         recipe = cache.get(sig) if sig is not None else None
         if recipe is not None:
             self._run_recipe(recipe, group, live)
+            self._record_pure(recipe, group, live)
             return
         recipe = self._build_and_run(group, live, dead)
+        self._record_pure(recipe, group, live)
         if sig is not None and recipe is not None:
             if len(cache) > 128:
                 cache.clear()
             cache[sig] = recipe
+
+    def _record_pure(self, recipe, group, live):
+        """Provenance for rematerialisation (common.remat): store a recipe
+        on every array this group left holding a cheap pure function of
+        the index.  Called only from _execute_group, after the group ran in
+        program order — a sealed producer runs late (execute_staged), after
+        its consumer's writes were registered, so it records nothing.  The
+        analysis depends on the group structure alone and is cached with
+        the execution recipe: a group with no such array costs one test."""
+        targets = recipe.pure_targets
+        if targets is None:
+            targets = recipe.pure_targets = deferred.pure_targets(group, live)
+        if targets:
+            deferred.record_pure(group, live, targets)
 
     def _run_recipe(self, recipe, group, live):
         """Re-run a cached recipe against the current group's backing
@@ -256,7 +274,7 @@ class Runtime:
             msgs = [(dst, src, live[owner].bd, bx, tgt)
                     for (dst, src, owner, bx, tgt) in recipe.comm_msgs]
             state = self._comms_begin(msgs, recipe.temp_geom)
-        from .common import ntiming
+        ntiming = common.ntiming
         tl = time.perf_counter() if ntiming else 0.0
         if recipe.units is not None:
             # overlapped split: interior unit(s) launch while the
@@ -687,6 +705,7 @@ class Runtime:
             self.backend.alloc_container(bd, self)
             bd.constructed = True
             bd.flex = False
+        bd.pure = None      # host data overwrites any index-pure content
         core = self.core_box(bd, self.rank)
         if core is not None:
             sl = tuple(slice(int(core[0, i]), int(core[1, i]) + 1)

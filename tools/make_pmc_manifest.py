@@ -34,6 +34,12 @@ def per_kernel_avg(path):
     with open(path) as f:
         for row in csv.DictReader(f):
             name = row["Kernel_Name"].strip('"')
+            if "Avg_Counter_Value" in row:
+                # tools/rocpd_stats.py summary: one row per kernel
+                n = int(row["Launches"])
+                sums[name] += float(row["Avg_Counter_Value"]) * n
+                counts[name] += n
+                continue
             sums[name] += float(row["Counter_Value"])
             counts[name] += 1
     return {k: sums[k] / counts[k] for k in sums}, dict(counts)

@@ -235,6 +235,65 @@ __global__ __launch_bounds__(256) void k_1r3w_ntl(const double *__restrict__ A,
          *(d2_t *)&B[vb] = b; *(d2_t *)&C[vb] = c; *(d2_t *)&D[vb] = d;)
 }
 
+// ---- store-only shapes: the flagship once its index-pure input is
+// recomputed instead of read (index -> (double)i*s -> rt_sincos -> three
+// 16 B/lane store streams, no load).  k_store3 above is their ceiling.
+
+__global__ __launch_bounds__(256) void k_store3_nt(double *__restrict__ B, double *__restrict__ C,
+                                                   double *__restrict__ D, i64 n) {
+    d2_t one = {1.0, 2.0};
+    LOOP(__builtin_nontemporal_store(one, (d2_t *)&B[vb]);
+         __builtin_nontemporal_store(one, (d2_t *)&C[vb]);
+         __builtin_nontemporal_store(one, (d2_t *)&D[vb]);)
+}
+
+// per-lane i64 -> f64 conversion, as the generator emits it
+#define REMAT_BODY(X0, X1)                                               \
+    double s0, c0, s1, c1;                                               \
+    rt_sincos((X0), &s0, &c0); rt_sincos((X1), &s1, &c1);                \
+    d2_t b, c, d;                                                        \
+    b[0] = s0; b[1] = s1; c[0] = c0; c[1] = c1;                          \
+    d[0] = s0 * s0 + c0 * c0; d[1] = s1 * s1 + c1 * c1;
+
+__global__ __launch_bounds__(256) void k_remat(double *__restrict__ B, double *__restrict__ C,
+                                               double *__restrict__ D, i64 n, i64 gs, double s) {
+    LOOP(REMAT_BODY((double)(gs + vb) * s, (double)(gs + vb + 1) * s)
+         *(d2_t *)&B[vb] = b; *(d2_t *)&C[vb] = c; *(d2_t *)&D[vb] = d;)
+}
+
+__global__ __launch_bounds__(256) void k_remat_nt(double *__restrict__ B, double *__restrict__ C,
+                                                  double *__restrict__ D, i64 n, i64 gs, double s) {
+    LOOP(REMAT_BODY((double)(gs + vb) * s, (double)(gs + vb + 1) * s)
+         __builtin_nontemporal_store(b, (d2_t *)&B[vb]);
+         __builtin_nontemporal_store(c, (d2_t *)&C[vb]);
+         __builtin_nontemporal_store(d, (d2_t *)&D[vb]);)
+}
+
+// one conversion per vector iteration; lane 1 by an exact add (bit-identical
+// while the index stays below 2^53)
+__global__ __launch_bounds__(256) void k_remat_hoist(double *__restrict__ B, double *__restrict__ C,
+                                                     double *__restrict__ D, i64 n, i64 gs,
+                                                     double s) {
+    LOOP(const double x0 = (double)(gs + vb);
+         REMAT_BODY(x0 * s, (x0 + 1.0) * s)
+         *(d2_t *)&B[vb] = b; *(d2_t *)&C[vb] = c; *(d2_t *)&D[vb] = d;)
+}
+
+// conversion carried across the grid-stride loop: converted once per
+// thread, then advanced by the (exactly representable) stride
+__global__ __launch_bounds__(256) void k_remat_carry(double *__restrict__ B, double *__restrict__ C,
+                                                     double *__restrict__ D, i64 n, i64 gs,
+                                                     double s) {
+    i64 vb = ((i64)blockIdx.x * 256 + threadIdx.x) * 2;
+    const i64 xs = (i64)gridDim.x * 256 * 2;
+    double x0 = (double)(gs + vb);
+    const double dx = (double)xs;
+    for (; vb + 2 <= n; vb += xs, x0 += dx) {
+        REMAT_BODY(x0 * s, (x0 + 1.0) * s)
+        *(d2_t *)&B[vb] = b; *(d2_t *)&C[vb] = c; *(d2_t *)&D[vb] = d;
+    }
+}
+
 template <typename F>
 static double timeit(F f, int iters) {
     hipEvent_t e0, e1;
@@ -300,5 +359,18 @@ int main(int argc, char **argv) {
         hipLaunchKernelGGL(k_1r3w_sc1, dim3(grid), dim3(256), 0, 0, A, B, C, D, n));
     RUN("1r3w_ntl", n * 32.0,
         hipLaunchKernelGGL(k_1r3w_ntl, dim3(grid), dim3(256), 0, 0, A, B, C, D, n));
+    // store-only shapes (24 B/elem, no load)
+    const i64 gs = 0;
+    const double sc = 0.001;
+    RUN("store3_nt", n * 24.0,
+        hipLaunchKernelGGL(k_store3_nt, dim3(grid), dim3(256), 0, 0, B, C, D, n));
+    RUN("remat", n * 24.0,
+        hipLaunchKernelGGL(k_remat, dim3(grid), dim3(256), 0, 0, B, C, D, n, gs, sc));
+    RUN("remat_nt", n * 24.0,
+        hipLaunchKernelGGL(k_remat_nt, dim3(grid), dim3(256), 0, 0, B, C, D, n, gs, sc));
+    RUN("remat_hoist", n * 24.0,
+        hipLaunchKernelGGL(k_remat_hoist, dim3(grid), dim3(256), 0, 0, B, C, D, n, gs, sc));
+    RUN("remat_carry", n * 24.0,
+        hipLaunchKernelGGL(k_remat_carry, dim3(grid), dim3(256), 0, 0, B, C, D, n, gs, sc));
     return 0;
 }
