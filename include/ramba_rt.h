@@ -17,6 +17,8 @@
  *   rt_copy_box       — shard sub-box pack/unpack for the part/halo
  *                       exchange (comm_queues puts at ramba.py:3656,
  *                       getborder ramba.py:1260) and gather (get_view 2160)
+ *   rt_take_rows      — indexed row gather for a[int_array] / take
+ *                       (all2all getitem worker, ramba.py:3960)
  *   rt_stream_sync /
  *   rt_device_sync    — worker-side completion (sync, ramba.py:9843)
  *   rt_event_*        — hot-loop timing (add_time, ramba.py:945-1022)
@@ -113,6 +115,33 @@ int rt_mask_compact(uintptr_t stream, const void *a, const void *m,
 int rt_flat_copy(uintptr_t stream, void *boxed, void *dense, int nd,
                  const int64_t *shape, const int64_t *strides,
                  int64_t flat0, int64_t n, int elemsize, int scatter);
+
+/* Indexed row gather / placement — the data movement of integer-array
+ * getitem and take() (reference all2all getitem worker,
+ * ramba/ramba.py:3960, getitem 6443-6545):
+ *     dst[dr(k)] = src[sr(k)]   for k in [0, n)
+ * where a "row" is a strided box of up to 3 inner axes; sr(k) =
+ * src_rows ? src_rows[k] : k, likewise dr(k).  A source row in
+ * [-src_nrows, 0) wraps once (NumPy negative index).  dst/src point at row
+ * 0; strides are in elements; src_rows/dst_rows are device int64[n].
+ * elemsize in {1,2,4,8}.  Rows outside [0,src_nrows) / [0,dst_nrows) are
+ * skipped and counted in *bad (device uint32, may be NULL).  Arguments are
+ * validated before any HIP call; n == 0 returns 0 without launching. */
+int rt_take_rows(uintptr_t stream, void *dst, const void *src,
+                 const int64_t *src_rows, const int64_t *dst_rows, int64_t n,
+                 int64_t src_nrows, int64_t dst_nrows, int nd_inner,
+                 const int64_t *inner_shape, const int64_t *src_strides,
+                 const int64_t *dst_strides, int64_t src_row_stride,
+                 int64_t dst_row_stride, int elemsize, void *bad);
+
+/* The kernel rt_take_rows picks for a geometry: 0 = narrow (one thread per
+ * element, rows under 256 B), 1 = wide (one wave per row) with 16-byte
+ * accesses, 2 = wide scalar; -1 on invalid arguments.  Host arithmetic
+ * only. */
+int rt_take_regime(const void *dst, const void *src, int nd_inner,
+                   const int64_t *inner_shape, const int64_t *src_strides,
+                   const int64_t *dst_strides, int64_t src_row_stride,
+                   int64_t dst_row_stride, int elemsize);
 
 int rt_stream_sync(uintptr_t stream);
 int rt_device_sync(void);

@@ -49,11 +49,32 @@ def init(backend=None, world_size=None, rank=None):
         # RAMBA_FORCE_PG=1 initialises the process group even at world 1
         # (world-1 RCCL transport tests on a single-GPU box)
         backend.init_process_group(rank, world)
+        _register_pg_teardown()
 
     rt = Runtime(backend, rank=rank, world=world)
     backend.attach(rt)
     _deferred.set_runtime(rt)
     _initialized["done"] = True
+
+
+def _destroy_process_group():
+    try:
+        import torch.distributed as dist
+        if dist.is_initialized():
+            dist.destroy_process_group()
+    except Exception:
+        pass
+
+
+def _register_pg_teardown():
+    """Tear the process group down before the interpreter does: a rank that
+    exits with the transport's worker threads still joinable aborts in
+    their destructors ("terminate called without an active exception"),
+    after its work is done and whatever its result was."""
+    if not _initialized.get("pg_atexit"):
+        import atexit
+        atexit.register(_destroy_process_group)
+        _initialized["pg_atexit"] = True
 
 
 def _auto_init():

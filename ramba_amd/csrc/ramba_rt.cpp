@@ -1516,3 +1516,318 @@ extern "C" int rt_flat_copy(uintptr_t stream, void *boxed, void *dense,
             return 1;
     }
 }
+
+// ---------------------------------------------------------------------------
+// indexed row gather / placement (integer-array getitem and take; the
+// reference's all2all getitem worker, ramba/ramba.py:3960, moves per-element
+// lists — here the unit is a whole ROW of the axis-0-split source).
+//     dst[dr(k)] = src[sr(k)]   for k in [0, n)
+// A row is a strided box of up to 3 inner axes (shard containers pad the
+// innermost axis, message buffers are dense).  Every row number is checked
+// against src_nrows / dst_nrows BEFORE an address is formed; a bad row is
+// skipped and counted in *bad.
+// ---------------------------------------------------------------------------
+
+namespace {
+
+struct TakeArgs {
+    int64_t n, src_nrows, dst_nrows;
+    int64_t src_rs, dst_rs;     // row strides, in kernel access units
+    int64_t sstr[3], dstr[3];   // inner strides (outer..inner), same units
+    uint32_t shp[3];            // inner extents, left-padded with 1
+    int nd;                     // real inner axes (0..3)
+};
+
+// src row for entry k (a negative source row wraps once, NumPy style) and
+// dst row; false when either is out of range
+__device__ __forceinline__ bool take_rows_of(const TakeArgs &g,
+                                             const int64_t *sr,
+                                             const int64_t *dr, int64_t k,
+                                             int64_t &s, int64_t &d) {
+    s = sr ? sr[k] : k;
+    if (s < 0) s += g.src_nrows;
+    d = dr ? dr[k] : k;
+    return (uint64_t)s < (uint64_t)g.src_nrows
+        && (uint64_t)d < (uint64_t)g.dst_nrows;
+}
+
+__device__ __forceinline__ void take_inner_off(const TakeArgs &g, uint32_t j,
+                                               int64_t &os, int64_t &od) {
+    // j = flat C-order position inside the row (in access units)
+    if (g.nd <= 1) {
+        os = (int64_t)j * g.sstr[2];
+        od = (int64_t)j * g.dstr[2];
+        return;
+    }
+    uint32_t q = j / g.shp[2], c2 = j - q * g.shp[2];
+    uint32_t c0 = q / g.shp[1], c1 = q - c0 * g.shp[1];
+    os = c0 * g.sstr[0] + c1 * g.sstr[1] + c2 * g.sstr[2];
+    od = c0 * g.dstr[0] + c1 * g.dstr[1] + c2 * g.dstr[2];
+}
+
+// NARROW regime: one thread per output element.  Consecutive threads take
+// consecutive entries k (ONE: the 1-D case, row = one element) or
+// consecutive elements of a row, so the index load and the dense side are
+// coalesced.  The only 64-bit division is block-uniform.
+template <typename T, bool ONE>
+__global__ __launch_bounds__(256) void take_narrow_kernel(
+    T *__restrict__ dst, const T *__restrict__ src,
+    const int64_t *__restrict__ sr, const int64_t *__restrict__ dr,
+    TakeArgs g, uint32_t re, unsigned int *bad) {
+    const int64_t total = g.n * (int64_t)re;
+    const int64_t nblk = (total + 255) / 256;
+    for (int64_t b = blockIdx.x; b < nblk; b += gridDim.x) {
+        const int64_t base = b * 256;
+        int64_t k;
+        uint32_t j = 0;
+        if (ONE) {
+            k = base + threadIdx.x;
+        } else {
+            const int64_t k0 = base / re;
+            const uint32_t t = (uint32_t)(base - k0 * re) + threadIdx.x;
+            const uint32_t dk = t / re;
+            j = t - dk * re;
+            k = k0 + dk;
+        }
+        if (k >= g.n) continue;
+        int64_t s, d;
+        if (!take_rows_of(g, sr, dr, k, s, d)) {
+            if (j == 0 && bad) atomicAdd(bad, 1u);
+            continue;
+        }
+        int64_t os = 0, od = 0;
+        if (!ONE) take_inner_off(g, j, os, od);
+        dst[d * g.dst_rs + od] = src[s * g.src_rs + os];
+    }
+}
+
+// WIDE regime: one wave per destination row, 4 rows in flight per wave
+// (the shape the MI355X guide measured for random whole rows); lanes sweep
+// the row in access units V — 16-byte uint4 when the geometry allows it,
+// one element otherwise.
+template <typename V>
+__global__ __launch_bounds__(256) void take_wide_kernel(
+    V *__restrict__ dst, const V *__restrict__ src,
+    const int64_t *__restrict__ sr, const int64_t *__restrict__ dr,
+    TakeArgs g, uint32_t units, unsigned int *bad) {
+    const uint32_t lane = threadIdx.x & 63;
+    const int64_t nwaves = (int64_t)gridDim.x * 4;
+    const int64_t ngroups = (g.n + 3) / 4;
+    for (int64_t grp = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+         grp < ngroups; grp += nwaves) {
+        int64_t so[4], dof[4];
+        bool ok[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int64_t k = grp * 4 + r;
+            so[r] = dof[r] = 0;
+            ok[r] = false;
+            if (k < g.n) {
+                int64_t s, d;
+                ok[r] = take_rows_of(g, sr, dr, k, s, d);
+                if (ok[r]) {
+                    so[r] = s * g.src_rs;
+                    dof[r] = d * g.dst_rs;
+                } else if (lane == 0 && bad) {
+                    atomicAdd(bad, 1u);
+                }
+            }
+        }
+        for (uint32_t u = lane; u < units; u += 64) {
+            int64_t os, od;
+            take_inner_off(g, u, os, od);
+            V v[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (ok[r]) v[r] = src[so[r] + os];
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (ok[r]) dst[dof[r] + od] = v[r];
+        }
+    }
+}
+
+// Regime choice (host): rows under 256 B go one thread per element — a
+// wave per row would leave most lanes idle; wider rows go one wave per row,
+// with 16-byte accesses iff the innermost extent, every stride (in bytes)
+// and both base pointers are multiples of 16.
+enum { TAKE_NARROW = 0, TAKE_WIDE_VEC = 1, TAKE_WIDE_SCALAR = 2 };
+
+int take_regime(const void *dst, const void *src, int nd_inner,
+                const int64_t *inner_shape, const int64_t *src_strides,
+                const int64_t *dst_strides, int64_t src_row_stride,
+                int64_t dst_row_stride, int elemsize) {
+    int64_t re = 1;
+    for (int d = 0; d < nd_inner; ++d) re *= inner_shape[d];
+    if (re * elemsize < 256) return TAKE_NARROW;
+    const int64_t es = elemsize;
+    bool vec = nd_inner >= 1
+        && (inner_shape[nd_inner - 1] * es) % 16 == 0
+        && src_strides[nd_inner - 1] == 1 && dst_strides[nd_inner - 1] == 1
+        && (src_row_stride * es) % 16 == 0 && (dst_row_stride * es) % 16 == 0
+        && reinterpret_cast<uintptr_t>(dst) % 16 == 0
+        && reinterpret_cast<uintptr_t>(src) % 16 == 0;
+    for (int d = 0; vec && d < nd_inner - 1; ++d)
+        vec = (src_strides[d] * es) % 16 == 0
+            && (dst_strides[d] * es) % 16 == 0;
+    return vec ? TAKE_WIDE_VEC : TAKE_WIDE_SCALAR;
+}
+
+int take_validate(const void *dst, const void *src, int64_t n, int nd_inner,
+                  const int64_t *inner_shape, const int64_t *src_strides,
+                  const int64_t *dst_strides, int elemsize) {
+    if (elemsize != 1 && elemsize != 2 && elemsize != 4 && elemsize != 8) {
+        set_error("rt_take_rows: bad elemsize");
+        return 1;
+    }
+    if (nd_inner < 0 || nd_inner > 3) {
+        set_error("rt_take_rows: nd_inner out of range");
+        return 1;
+    }
+    if (n < 0) {
+        set_error("rt_take_rows: negative n");
+        return 1;
+    }
+    if (n > 0 && (dst == nullptr || src == nullptr)) {
+        set_error("rt_take_rows: NULL dst/src");
+        return 1;
+    }
+    if (nd_inner > 0 && (!inner_shape || !src_strides || !dst_strides)) {
+        set_error("rt_take_rows: NULL inner geometry");
+        return 1;
+    }
+    int64_t re = 1;
+    for (int d = 0; d < nd_inner; ++d) {
+        if (inner_shape[d] < 0 || inner_shape[d] >= (1LL << 31)) {
+            set_error("rt_take_rows: inner extent out of range");
+            return 1;
+        }
+        re *= inner_shape[d];
+        if (re >= (1LL << 31)) {
+            set_error("rt_take_rows: row too large");
+            return 1;
+        }
+    }
+    return 0;
+}
+
+template <typename T>
+int take_launch(uintptr_t stream, void *dst, const void *src,
+                const int64_t *sr, const int64_t *dr, TakeArgs g,
+                int64_t re, int regime, void *bad) {
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    unsigned int *badp = static_cast<unsigned int *>(bad);
+    if (regime == TAKE_NARROW) {
+        int64_t blocks = (g.n * re + 255) / 256;
+        if (blocks > 65536) blocks = 65536;
+        if (re == 1)
+            hipLaunchKernelGGL((take_narrow_kernel<T, true>),
+                               dim3((unsigned)blocks), dim3(256), 0, st,
+                               static_cast<T *>(dst),
+                               static_cast<const T *>(src), sr, dr, g,
+                               (uint32_t)re, badp);
+        else
+            hipLaunchKernelGGL((take_narrow_kernel<T, false>),
+                               dim3((unsigned)blocks), dim3(256), 0, st,
+                               static_cast<T *>(dst),
+                               static_cast<const T *>(src), sr, dr, g,
+                               (uint32_t)re, badp);
+    } else {
+        // 4 waves per block, 4 rows per wave pass; 16 waves per CU on
+        // 256 CUs = 1024 resident blocks, the rest by grid stride
+        int64_t blocks = (g.n + 15) / 16;
+        if (blocks > 4096) blocks = 4096;
+        if (regime == TAKE_WIDE_VEC) {
+            const int64_t per = 16 / (int64_t)sizeof(T);
+            TakeArgs v = g;
+            v.src_rs /= per;
+            v.dst_rs /= per;
+            for (int d = 0; d < 2; ++d) {
+                v.sstr[d] /= per;
+                v.dstr[d] /= per;
+            }
+            v.shp[2] = (uint32_t)(g.shp[2] / per);
+            hipLaunchKernelGGL((take_wide_kernel<uint4>),
+                               dim3((unsigned)blocks), dim3(256), 0, st,
+                               static_cast<uint4 *>(dst),
+                               static_cast<const uint4 *>(src), sr, dr, v,
+                               (uint32_t)(re / per), badp);
+        } else {
+            hipLaunchKernelGGL((take_wide_kernel<T>),
+                               dim3((unsigned)blocks), dim3(256), 0, st,
+                               static_cast<T *>(dst),
+                               static_cast<const T *>(src), sr, dr, g,
+                               (uint32_t)re, badp);
+        }
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        set_error(std::string("take_rows launch: ") + hipGetErrorString(e));
+        return 1;
+    }
+    return 0;
+}
+
+}  // namespace
+
+// Which kernel rt_take_rows would run for this geometry: 0 = narrow (thread
+// per element), 1 = wide with 16-byte accesses, 2 = wide scalar; -1 on bad
+// arguments.  Pure host arithmetic (pointers are only tested for alignment).
+extern "C" int rt_take_regime(const void *dst, const void *src, int nd_inner,
+                              const int64_t *inner_shape,
+                              const int64_t *src_strides,
+                              const int64_t *dst_strides,
+                              int64_t src_row_stride, int64_t dst_row_stride,
+                              int elemsize) {
+    if (take_validate(dst, src, 0, nd_inner, inner_shape, src_strides,
+                      dst_strides, elemsize))
+        return -1;
+    return take_regime(dst, src, nd_inner, inner_shape, src_strides,
+                       dst_strides, src_row_stride, dst_row_stride,
+                       elemsize);
+}
+
+// dst / src point at row 0 (pre-offset to the core origin); strides are in
+// elements.  src_rows / dst_rows are device int64[n] or NULL (identity).
+extern "C" int rt_take_rows(uintptr_t stream, void *dst, const void *src,
+                            const int64_t *src_rows, const int64_t *dst_rows,
+                            int64_t n, int64_t src_nrows, int64_t dst_nrows,
+                            int nd_inner, const int64_t *inner_shape,
+                            const int64_t *src_strides,
+                            const int64_t *dst_strides,
+                            int64_t src_row_stride, int64_t dst_row_stride,
+                            int elemsize, void *bad) {
+    if (take_validate(dst, src, n, nd_inner, inner_shape, src_strides,
+                      dst_strides, elemsize))
+        return 1;
+    if (n == 0) return 0;
+    TakeArgs g;
+    g.n = n;
+    g.src_nrows = src_nrows;
+    g.dst_nrows = dst_nrows;
+    g.src_rs = src_row_stride;
+    g.dst_rs = dst_row_stride;
+    g.nd = nd_inner;
+    int64_t re = 1;
+    for (int d = 0; d < 3; ++d) {
+        const int s = d - (3 - nd_inner);
+        g.shp[d] = s >= 0 ? (uint32_t)inner_shape[s] : 1u;
+        g.sstr[d] = s >= 0 ? src_strides[s] : 0;
+        g.dstr[d] = s >= 0 ? dst_strides[s] : 0;
+        re *= g.shp[d];
+    }
+    if (re == 0) return 0;
+    const int regime = take_regime(dst, src, nd_inner, inner_shape,
+                                   src_strides, dst_strides, src_row_stride,
+                                   dst_row_stride, elemsize);
+    switch (elemsize) {
+        case 1: return take_launch<uint8_t>(stream, dst, src, src_rows,
+                                            dst_rows, g, re, regime, bad);
+        case 2: return take_launch<uint16_t>(stream, dst, src, src_rows,
+                                             dst_rows, g, re, regime, bad);
+        case 4: return take_launch<uint32_t>(stream, dst, src, src_rows,
+                                             dst_rows, g, re, regime, bad);
+        default: return take_launch<uint64_t>(stream, dst, src, src_rows,
+                                              dst_rows, g, re, regime, bad);
+    }
+}

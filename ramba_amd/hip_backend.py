@@ -92,6 +92,18 @@ def _load_lib():
                                  ctypes.POINTER(ctypes.c_int64),
                                  ctypes.c_int64, ctypes.c_int64,
                                  ctypes.c_int, ctypes.c_int]
+    _p64 = ctypes.POINTER(ctypes.c_int64)
+    lib.rt_take_rows.argtypes = [ctypes.c_size_t, ctypes.c_void_p,
+                                 ctypes.c_void_p, ctypes.c_void_p,
+                                 ctypes.c_void_p, ctypes.c_int64,
+                                 ctypes.c_int64, ctypes.c_int64,
+                                 ctypes.c_int, _p64, _p64, _p64,
+                                 ctypes.c_int64, ctypes.c_int64,
+                                 ctypes.c_int, ctypes.c_void_p]
+    lib.rt_take_regime.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
+                                   ctypes.c_int, _p64, _p64, _p64,
+                                   ctypes.c_int64, ctypes.c_int64,
+                                   ctypes.c_int]
     lib.rt_stream_sync.argtypes = [ctypes.c_size_t]
     return lib
 
@@ -300,7 +312,9 @@ class HipBackend:
                    tmp.element_size())
 
     def box_to_numpy(self, bd, rt, box):
-        return self.pack_box(bd, rt, box).cpu().numpy().astype(
+        host = self.pack_box(bd, rt, box).cpu()     # D2H syncs the stream
+        self._check_take_bad()
+        return host.numpy().astype(
             bd.dtype, copy=False).reshape(box_shape(box))
 
     def write_core_from_numpy(self, bd, rt, nparr):
@@ -464,6 +478,7 @@ class HipBackend:
 
     def sync(self):
         self.torch.cuda.synchronize()
+        self._check_take_bad()
 
 
 # ---------------------------------------------------------------------------
@@ -902,6 +917,110 @@ def _hb_flat_scatter(self, cont, off0, strides, shape, flat0, buf):
 
 HipBackend.flat_gather = _hb_flat_gather
 HipBackend.flat_scatter = _hb_flat_scatter
+
+
+# -- indexed row gather (a[int_array] / take; runtime.take_op) ---------------
+#
+# All row data movement is rt_take_rows: the gather of table rows into a
+# dense reply, the placement of replies, and the world-1 direct path
+# (container -> container).  The frontend validates every index, so the
+# kernel's bad-row counter stays zero; it is read only where the backend
+# synchronises anyway (sync / box_to_numpy) and raises if it is not.
+
+
+def _hb_take_cont_side(self, bd, rt):
+    """(pointer at core row 0, inner strides, row stride, local rows) of
+    the rank's container; the core spans axes 1.. fully (take_op checks)."""
+    d, _, cstr, pads = rt.shard_geometry(bd)
+    cont = self._cont(bd)
+    off = sum(pads[i] * cstr[i] for i in range(len(bd.shape)))
+    return (cont.data_ptr() + off * cont.element_size(), tuple(cstr[1:]),
+            cstr[0], int(d[1, 0] - d[0, 0] + 1))
+
+
+def _hb_take_dense_side(t):
+    st = t.stride()
+    return t.data_ptr(), tuple(st[1:]), st[0], int(t.shape[0])
+
+
+def _hb_take_launch(self, dst, src, inner_shape, src_rows, dst_rows, n,
+                    elemsize):
+    if n == 0:
+        return
+    if getattr(self, "_take_bad", None) is None:
+        self._take_bad = self.torch.zeros(1, dtype=self.torch.int32,
+                                          device="cuda")
+    self._take_dirty = True
+    (dptr, dstr, drs, dnrows), (sptr, sstr, srs, snrows) = dst, src
+    self._check(self.lib.rt_take_rows(
+        self._stream(), ctypes.c_void_p(dptr), ctypes.c_void_p(sptr),
+        ctypes.c_void_p(src_rows.data_ptr()) if src_rows is not None
+        else None,
+        ctypes.c_void_p(dst_rows.data_ptr()) if dst_rows is not None
+        else None,
+        int(n), snrows, dnrows, len(inner_shape), _i64arr(inner_shape),
+        _i64arr(sstr), _i64arr(dstr), srs, drs, elemsize,
+        ctypes.c_void_p(self._take_bad.data_ptr())), "rt_take_rows")
+
+
+def _hb_check_take_bad(self):
+    if not getattr(self, "_take_dirty", False):
+        return
+    self._take_dirty = False
+    nbad = int(self._take_bad.cpu().numpy()[0])
+    if nbad:
+        self._take_bad.zero_()
+        raise IndexError(
+            f"take: {nbad} row number(s) out of range reached the gather "
+            "kernel and were skipped (frontend validation was bypassed)")
+
+
+def _hb_take_index(self, idx_bd, rt):
+    """The rank's slice of a 1-D int64 index array, as a device tensor."""
+    d, _, _, pads = rt.shard_geometry(idx_bd)
+    if d is None:
+        return self.torch.empty(0, dtype=self.torch.int64, device="cuda")
+    n = int(d[1, 0] - d[0, 0] + 1)
+    return self._cont(idx_bd)[pads[0]:pads[0] + n]
+
+
+def _hb_gather_rows(self, src_bd, rt, rows, out=None, positions=None):
+    """Rows `rows` (local row numbers, device int64) of the rank's shard:
+    into a fresh dense (n,)+row_shape tensor, or, with `out`, into that
+    array's container core at rows positions[k] (rows 0..n-1 if None)."""
+    n = int(rows.numel())
+    cont = self._cont(src_bd)
+    inner = tuple(src_bd.shape[1:])
+    rows = rows.contiguous()
+    if out is None:
+        dense = self.torch.empty((n,) + inner, dtype=cont.dtype,
+                                 device="cuda")
+        dst = _hb_take_dense_side(dense)
+    else:
+        dense = None
+        dst = self._take_cont_side(out, rt)
+        if positions is not None:
+            positions = positions.contiguous()
+    self._take_launch(dst, self._take_cont_side(src_bd, rt), inner, rows,
+                      positions, n, cont.element_size())
+    return dense
+
+
+def _hb_place_rows(self, out_bd, rt, positions, dense):
+    """out[positions[k]] = dense[k] on the rank's container core."""
+    dense = dense.contiguous()
+    self._take_launch(self._take_cont_side(out_bd, rt),
+                      _hb_take_dense_side(dense), tuple(out_bd.shape[1:]),
+                      None, positions.contiguous(), int(dense.shape[0]),
+                      dense.element_size())
+
+
+HipBackend._take_cont_side = _hb_take_cont_side
+HipBackend._take_launch = _hb_take_launch
+HipBackend._check_take_bad = _hb_check_take_bad
+HipBackend.take_index = _hb_take_index
+HipBackend.gather_rows = _hb_gather_rows
+HipBackend.place_rows = _hb_place_rows
 
 
 # -- cross-stage fusion (staged/tiled kernel; ramba_amd/staged.py) -----------

@@ -189,6 +189,10 @@ class ndarray:
             deferred.flush()
             out_bd = rt.mask_compact_op(ta.bdarray, tm.bdarray)
             return ndarray(out_bd, View.identity(out_bd.shape))
+        # integer-array (gather) getitem: detected before the basic-index
+        # cache below, which stays untouched
+        if _has_index_array(index):
+            return _take_getitem(self, index)
         if not isinstance(index, tuple):
             index = (index,)
         if all(isinstance(i, (int, np.integer)) for i in index) \
@@ -257,6 +261,12 @@ class ndarray:
                                      self, dt),
                             empty_like=empty_like)
             return
+        if _has_index_array(index):
+            # self[index] below would gather into a temporary copy and the
+            # assignment would silently land there
+            raise NotImplementedError(
+                "assignment through an integer index array (a[idx] = v) "
+                "is not supported")
         view = self[index] if not (isinstance(index, tuple) and index == ()) \
             else self
         if isinstance(view, (np.generic, numbers.Number)):
@@ -645,6 +655,9 @@ class ndarray:
             order.insert(d, s_)
         return self.transpose(order)
 
+    def take(self, indices, axis=None, out=None, mode="raise"):
+        return take(self, indices, axis=axis, out=out, mode=mode)
+
     def rollaxis(self, axis, start=0):
         n = self.ndim
         axis = axis + n if axis < 0 else axis
@@ -659,6 +672,228 @@ class ndarray:
 
 
 deferred.NDARRAY_CLS = ndarray   # fast leaf test in deferred._subst
+
+
+# ---------------------------------------------------------------------------
+# integer-array indexing: a[idx] and take (reference getitem index-array
+# branch, ramba.py:6443-6545 + dim_sizes_from_index 7668-7749).  Every
+# supported form is reduced to "gather rows along axis 0 of an axis-0-split
+# array by a 1-D int64 index" (runtime.take_op); shapes follow NumPy,
+# including the case the reference gets wrong (a scalar int in the tuple
+# counts as an advanced index).
+# ---------------------------------------------------------------------------
+
+_BASIC_INDEX = (int, slice, type(None), type(Ellipsis), np.integer)
+
+
+def _is_index_array(ix):
+    if isinstance(ix, (list, tuple)):
+        return True
+    if isinstance(ix, ndarray):
+        return True
+    return isinstance(ix, np.ndarray) and ix.ndim > 0
+
+
+def _has_index_array(index):
+    """True when `index` holds a list / array element (anything but the
+    whole-array boolean masks, which the callers handle first)."""
+    if isinstance(index, tuple):
+        for ix in index:
+            if not isinstance(ix, _BASIC_INDEX) and _is_index_array(ix):
+                return True
+        return False
+    if isinstance(index, _BASIC_INDEX):
+        return False
+    if isinstance(index, (ndarray, np.ndarray)) and index.dtype == np.bool_:
+        return False
+    return _is_index_array(index)
+
+
+def _classify_index(index):
+    """(expanded tuple, position of the one index array, the array)."""
+    if not isinstance(index, tuple):
+        index = (index,)
+    apos = None
+    for k, ix in enumerate(index):
+        if isinstance(ix, _BASIC_INDEX) \
+                or (isinstance(ix, np.ndarray) and ix.ndim == 0):
+            continue                    # 0-d array: a scalar index
+        if not _is_index_array(ix):
+            raise IndexError(f"unsupported index element {ix!r}")
+        if apos is not None:
+            raise IndexError(
+                "indexing with two or more index arrays is unsupported "
+                "(one integer array per index)")
+        apos = k
+    if any(ix is None for ix in index):
+        raise IndexError(
+            "None (newaxis) together with an index array is unsupported")
+    arr = index[apos]
+    if isinstance(arr, (list, tuple)):
+        arr = np.asarray(arr)
+        if arr.size == 0:
+            arr = arr.astype(np.int64)
+        elif arr.dtype == np.bool_:
+            raise IndexError(
+                "a boolean list as an index is unsupported (use a boolean "
+                "ramba_amd / NumPy array of the array's shape)")
+    if arr.dtype == np.bool_:
+        raise IndexError(
+            "a boolean array inside an index tuple, or beside other "
+            "indices, is unsupported (use a[mask] with a full-shape mask)")
+    if np.dtype(arr.dtype).kind not in "iu":
+        raise IndexError(
+            "arrays used as indices must be of integer (or boolean) type")
+    if arr.ndim == 0:
+        raise IndexError("0-d index arrays are unsupported")
+    index = tuple(int(ix) if isinstance(ix, np.ndarray) else ix
+                  for ix in index[:apos]) + (arr,) + tuple(
+        int(ix) if isinstance(ix, np.ndarray) else ix
+        for ix in index[apos + 1:])
+    return index, apos, arr
+
+
+def _index_to_i64(arr, rt):
+    """The index as a constructed 1-D int64 ramba array of length arr.size
+    on contiguous_divisions (N-D indices ravelled); other integer dtypes are
+    cast through the fused engine, host data comes in by scatter."""
+    from .common import contiguous_divisions
+    m = int(arr.size)
+    cdivs = contiguous_divisions(rt.world, (m,))
+    bd = deferred.bdarray((m,), np.dtype(np.int64), cdivs, default_border,
+                          flex=False)
+    out = ndarray(bd, View.identity((m,)))
+    if isinstance(arr, np.ndarray):
+        if arr.dtype == np.uint64 and m and int(arr.max()) > np.iinfo(
+                np.int64).max:
+            return None, int(arr.max())
+        deferred.flush()
+        rt.scatter_numpy(bd, np.ascontiguousarray(
+            arr.reshape(-1), dtype=np.int64))
+        return out, None
+    if arr.ndim != 1:
+        arr = arr.reshape(m)
+    if (arr.dtype == np.int64 and arr.bdarray.constructed
+            and arr.view.is_identity_for(arr.bdarray.shape)
+            and np.array_equal(arr.bdarray.divisions, cdivs)):
+        return arr, None
+    deferred.add_op(out, "=", arr if arr.dtype == np.int64
+                    else ir.Cast(arr, np.dtype(np.int64)),
+                    empty_like=empty_like)
+    return out, None
+
+
+def _take_source(src, rt):
+    """`src` (indexed axis in front) as a constructed array whose shards
+    are axis-0 splits spanning axes 1..: itself when it already is one (so
+    a table gather pays no table copy), else a copy onto
+    contiguous_divisions through the fused engine."""
+    bd = src.bdarray
+    if bd.constructed and src.view.is_identity_for(bd.shape):
+        ok = True
+        for r in range(rt.world):
+            cb = rt.core_box(bd, r)
+            if cb is None:
+                continue
+            for dax in range(1, len(bd.shape)):
+                if not (cb[0, dax] == 0
+                        and cb[1, dax] == bd.shape[dax] - 1):
+                    ok = False
+        if ok:
+            return src
+    from .common import contiguous_divisions
+    t_bd = deferred.bdarray(src.shape, src.dtype,
+                            contiguous_divisions(rt.world, src.shape),
+                            default_border, flex=False)
+    tmp = ndarray(t_bd, View.identity(src.shape))
+    deferred.add_op(tmp, "=", src, empty_like=empty_like)
+    deferred.flush()
+    return tmp
+
+
+def _take_getitem(self, index):
+    index, apos, arr = _classify_index(index)
+    # the basic terms, with slice(None) at the array's position (a view)
+    basic = index[:apos] + (slice(None),) + index[apos + 1:]
+    v1 = self._with_view(self.view.apply_index(basic))
+    # expanded positions: the indexed axis of `self` (for messages) and of
+    # v1, and whether the advanced indices (array + ints) are adjacent
+    nconsume = len([ix for ix in index if ix is not Ellipsis])
+    exp = []
+    for ix in index:
+        if ix is Ellipsis:
+            exp.extend([slice(None)] * (self.ndim - (nconsume)))
+        else:
+            exp.append(ix)
+    exp.extend([slice(None)] * (self.ndim - len(exp)))
+    axis_self = next(k for k, ix in enumerate(exp) if ix is arr)
+    ax = len([ix for ix in exp[:axis_self] if isinstance(ix, slice)])
+    adv = [k for k, ix in enumerate(exp) if not isinstance(ix, slice)]
+    adjacent = adv[-1] - adv[0] + 1 == len(adv)
+    n_axis = self.shape[axis_self]
+    rest = v1.shape[:ax] + v1.shape[ax + 1:]
+    if len(rest) > 3:
+        raise NotImplementedError(
+            "index-array getitem supports rows of up to 3 axes")
+    ishape = tuple(arr.shape)
+    m = int(arr.size)
+    place = ax if adjacent else 0
+    final = rest[:place] + ishape + rest[place:]
+
+    rt = deferred.get_runtime()
+    if m:
+        # bounds: one fused min+max over the index, one flush; every rank
+        # reaches the same decision before anything is gathered
+        idx, bad = _index_to_i64(arr, rt)
+        if idx is not None:
+            p_lo = deferred.add_reduction(idx, "min", np.dtype(np.int64))
+            p_hi = deferred.add_reduction(idx, "max", np.dtype(np.int64))
+            deferred.flush()
+            lo = int(rt.finish_reduction(p_lo))
+            hi = int(rt.finish_reduction(p_hi))
+            bad = lo if lo < -n_axis else hi if hi >= n_axis else None
+        if bad is not None:
+            raise IndexError(f"index {bad} is out of bounds for axis "
+                             f"{axis_self} with size {n_axis}")
+    if m == 0 or any(s == 0 for s in rest):
+        return zeros(final, dtype=self.dtype)
+    deferred.flush()
+    # (the wrapper keeps a temporary copy's shard alive across the gather)
+    src = _take_source(v1.moveaxis(ax, 0) if ax else v1, rt)
+    out_bd = rt.take_op(src.bdarray, idx.bdarray)
+    res = ndarray(out_bd, View.identity(out_bd.shape))
+    if len(ishape) != 1:
+        res = res.reshape(ishape + rest)
+    if place:
+        k = len(ishape)
+        res = res.moveaxis(list(range(k)), list(range(place, place + k)))
+    return res
+
+
+def take(a, indices, axis=None, out=None, mode="raise"):
+    """numpy.take for ramba arrays (reference: the index-array getitem,
+    ramba.py:6443-6545); axis=None takes from the ravelled array."""
+    if out is not None:
+        raise NotImplementedError("take: out= is not supported")
+    if mode != "raise":
+        raise NotImplementedError(f"take: mode={mode!r} is not supported")
+    if not isinstance(a, ndarray):
+        if isinstance(indices, ndarray):
+            indices = indices.asarray()
+        return np.take(a, indices, axis=axis)
+    if axis is None:
+        if a.ndim != 1:
+            a = a.ravel()
+        axis = 0
+    axis = int(axis)
+    if not (-a.ndim <= axis < a.ndim):
+        raise np.exceptions.AxisError(axis, a.ndim)
+    axis = axis + a.ndim if axis < 0 else axis
+    if isinstance(indices, (numbers.Integral, np.integer)) \
+            or (isinstance(indices, np.ndarray) and indices.ndim == 0
+                and indices.dtype.kind in "iu"):
+        indices = int(indices)
+    return a[(slice(None),) * axis + (indices,)]
 
 
 # -- attach the op tables (reference make_method loops, ramba.py:7893-7973) --
@@ -1354,6 +1589,8 @@ def ravel(a):
 ndarray._ARRAY_FUNC.update({
     "reshape": lambda a, shape, **kw: a.reshape(shape),
     "ravel": lambda a, **kw: a.ravel(),
+    "take": lambda a, indices, axis=None, out=None, mode="raise":
+        take(a, indices, axis=axis, out=out, mode=mode),
 })
 
 

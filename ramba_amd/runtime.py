@@ -1147,3 +1147,84 @@ def reshape_op(self, arr, newshape):
 
 
 Runtime.reshape_op = reshape_op
+
+# ---------------------------------------------------------------------------
+# integer-array getitem / take (reference getitem_array_executor index-array
+# branch, ramba.py:6443-6545, and its all2all worker, ramba.py:3960).  The
+# frontend reduces every form to ONE primitive: gather rows along axis 0 of
+# an axis-0-split array by a validated 1-D int64 index.  World 1 is one
+# local gather launch.  World > 1 is a deterministic request/reply exchange:
+# each rank buckets its index slice by owning rank, the world x world count
+# matrix is allgathered (so both ends of every message know its length),
+# row-number requests go out, owners gather the rows into dense replies,
+# replies come back and are placed at their output rows.  The rank's own
+# bucket never touches the wire.  The reference ships per-element index
+# lists and values; here the unit is a whole row.
+# ---------------------------------------------------------------------------
+
+def take_op(self, src_bd, idx_bd):
+    from . import rowgather as _take
+    from .common import contiguous_divisions
+    assert len(idx_bd.shape) == 1 and idx_bd.dtype == np.int64
+    nrows, row_shape = src_bd.shape[0], tuple(src_bd.shape[1:])
+    m = idx_bd.shape[0]
+    owners = []                 # (axis-0 start, rank) of non-empty shards
+    for r in range(self.world):
+        cb = self.core_box(src_bd, r)
+        if cb is None:
+            continue
+        for dax in range(1, len(src_bd.shape)):
+            assert cb[0, dax] == 0 and cb[1, dax] == src_bd.shape[dax] - 1, \
+                "take_op: source shards must span axes 1.. (frontend " \
+                "repartitions first)"
+        owners.append((int(cb[0, 0]), r))
+    owners.sort()
+
+    out_shape = (m,) + row_shape
+    out_bd = deferred.bdarray(out_shape, src_bd.dtype,
+                              contiguous_divisions(self.world, out_shape),
+                              default_border, flex=False)
+    self.backend.alloc_container(out_bd, self)
+    out_bd.constructed = True
+    assert np.array_equal(out_bd.divisions[:, :, 0], idx_bd.divisions[:, :, 0])
+
+    hooks = _take.hooks_for(self.backend)
+    rows = hooks.take_index(idx_bd, self)
+    if self.world == 1:
+        hooks.gather_rows(src_bd, self, rows, out=out_bd)
+        return out_bd
+
+    me = self.rank
+    pos, lrows = _take.bucket_rows(rows, [s for s, _ in owners],
+                                   [r for _, r in owners], nrows, self.world)
+    # counts[r][s] = rows rank r requests from rank s
+    counts = np.zeros((self.world, self.world), dtype=np.int64)
+    for s in range(self.world):
+        col = self.backend.allgather_scalars(np.int64(pos[s].numel()),
+                                             np.int64)
+        counts[:, s] = [int(c) for c in col]
+
+    # requests: row numbers local to the owner, in index order
+    sends = [(s, lrows[s]) for s in range(self.world)
+             if s != me and counts[me, s]]
+    reqs = [(r, self.backend.new_message_buffer((int(counts[r, me]),),
+                                                np.int64))
+            for r in range(self.world) if r != me and counts[r, me]]
+    if sends or reqs:
+        self.backend.exchange(sends, reqs)
+    # replies: dense (count,) + row_shape per requester
+    sends = [(r, hooks.gather_rows(src_bd, self, buf)) for (r, buf) in reqs]
+    reps = [(s, self.backend.new_message_buffer(
+                (int(counts[me, s]),) + row_shape, src_bd.dtype))
+            for s in range(self.world) if s != me and counts[me, s]]
+    if counts[me, me]:
+        hooks.gather_rows(src_bd, self, lrows[me], out=out_bd,
+                          positions=pos[me])
+    if sends or reps:
+        self.backend.exchange(sends, reps)
+    for (s, buf) in reps:
+        hooks.place_rows(out_bd, self, pos[s], buf)
+    return out_bd
+
+
+Runtime.take_op = take_op

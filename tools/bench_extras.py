@@ -1,8 +1,11 @@
 """Timings for the round-1 extension kernels at streaming scale
-(axis cumsum / mask-getitem / reshape).  Not the judged bench line —
-evidence for DESIGN.md §9's extra rows; run under rocprofv3 --stats for
-the per-kernel summary committed to profiles/."""
+(axis cumsum / mask-getitem / reshape) and for the indexed row gather
+(`python tools/bench_extras.py take` runs that leg alone).  Not the judged
+bench line — evidence for DESIGN.md §9's extra rows; run under rocprofv3
+--stats for the per-kernel summary committed to profiles/."""
 
+import ctypes
+import json
 import sys
 import time
 
@@ -26,8 +29,99 @@ def timed(label, fn, algo_bytes, iters=3):
     return r
 
 
+def take_leg(repeats=5, inner=10):
+    """rt_take_rows on one GPU against torch.index_select on the same
+    tensors (an independent yardstick).  Per case: `repeats` windows of
+    `inner` launches each, the two implementations alternating, timed with
+    rt_event_*; effective GB/s = (index bytes + 2 x gathered bytes) / time.
+    (a) 1e8 random int64 indices into a 1e8-element fp64 vector (narrow
+    regime); (b) 4e6 random rows of a (4e6, 128) fp64 table: 1 KiB rows,
+    4 GB table, far past the Infinity Cache (wide 16-byte regime)."""
+    import torch
+    from ramba_amd import deferred
+    rt = deferred.get_runtime()
+    be = rt.backend
+    lib = be.lib
+    lib.rt_event_create.argtypes = [ctypes.POINTER(ctypes.c_void_p)]
+    lib.rt_event_record.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
+    lib.rt_event_elapsed.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.POINTER(ctypes.c_float)]
+    ev0, ev1 = ctypes.c_void_p(), ctypes.c_void_p()
+    be._check(lib.rt_event_create(ctypes.byref(ev0)), "rt_event_create")
+    be._check(lib.rt_event_create(ctypes.byref(ev1)), "rt_event_create")
+
+    def window(fn):
+        ms = ctypes.c_float()
+        be._check(lib.rt_event_record(ev0, be._stream()), "rt_event_record")
+        for _ in range(inner):
+            fn()
+        be._check(lib.rt_event_record(ev1, be._stream()), "rt_event_record")
+        be._check(lib.rt_event_elapsed(ev0, ev1, ctypes.byref(ms)),
+                  "rt_event_elapsed")
+        return ms.value / inner
+
+    def core(arr):
+        bd = arr.bdarray
+        _, _, _, pads = rt.shard_geometry(bd)
+        sl = tuple(slice(p, p + s) for p, s in zip(pads, bd.shape))
+        return be._cont(bd)[sl]
+
+    cases = [("take_1d_1e8_fp64", (100_000_000,), 100_000_000),
+             ("take_rows_4e6x128_fp64", (4_000_000, 128), 4_000_000)]
+    for name, shape, m in cases:
+        if len(shape) == 1:
+            table = ra.arange(shape[0]) * 1.0
+        else:
+            table = ra.fromfunction(lambda i, j: i * 128.0 + j, shape)
+        idx = ra.zeros(m, dtype=np.int64)
+        out = ra.zeros((m,) + shape[1:])
+        ra.sync()
+        rows = be.take_index(idx.bdarray, rt)
+        rows.copy_(torch.randint(0, shape[0], (m,), device="cuda"))
+        t_core, o_core = core(table), core(out)
+        ref = torch.empty((m,) + shape[1:], dtype=torch.float64,
+                          device="cuda")
+
+        def hand():
+            be.gather_rows(table.bdarray, rt, rows, out=out.bdarray)
+
+        def yard():
+            torch.index_select(t_core, 0, rows, out=ref)
+
+        hand(), yard()                      # warm-up of both shapes
+        torch.cuda.synchronize()
+        assert torch.equal(o_core, ref), name
+        t_hand, t_yard = [], []
+        for _ in range(repeats):            # alternate the two
+            t_hand.append(window(hand))
+            t_yard.append(window(yard))
+        row_bytes = 8 * int(np.prod(shape[1:], dtype=np.int64))
+        nbytes = m * 8 + 2 * m * row_bytes
+
+        def gbs(ms):
+            return nbytes / (ms * 1e-3) / 1e9
+
+        rec = {"case": name, "bytes": nbytes, "repeats": repeats,
+               "launches_per_window": inner}
+        for tag, ts in (("rt_take_rows", t_hand), ("index_select", t_yard)):
+            ts = sorted(ts)
+            rec[tag] = {"ms_median": round(ts[len(ts) // 2], 4),
+                        "ms_min": round(ts[0], 4),
+                        "ms_max": round(ts[-1], 4),
+                        "gbs_median": round(gbs(ts[len(ts) // 2]), 1),
+                        "gbs_min": round(gbs(ts[-1]), 1),
+                        "gbs_max": round(gbs(ts[0]), 1)}
+        print("TAKE " + json.dumps(rec), flush=True)
+        del table, idx, out, ref, rows, t_core, o_core
+        ra.sync()
+
+
 def main():
     ra.init()
+    if sys.argv[1:] == ["take"]:
+        take_leg()
+        print("done", flush=True)
+        return
     n = 16384
     # N-D axis cumsum, both mappings (thread-per-line / wave-per-line)
     A = ra.fromfunction(lambda i, j: (i * 3 + j) * 1e-9, (n, n))
@@ -52,6 +146,8 @@ def main():
     ra.sync()
     timed("reshape 1e9 -> (31250, 32000) fp64 [rt_flat_copy]",
           lambda: C.reshape(31250, 32000), m * 32)
+    del A, B, Bf, C
+    take_leg()
     print("done", flush=True)
 
 
