@@ -34,6 +34,12 @@ def eval_expr(e, env, itershape, global_start):
     if isinstance(e, ir.Bin):
         a = eval_expr(e.a, env, itershape, global_start)
         b = eval_expr(e.b, env, itershape, global_start)
+        if np.dtype(e.dtype) == np.float32:
+            # a Python-float scalar is weak (NEP 50): NumPy and the HIP
+            # kernels round it to float32 BEFORE the operation; computing
+            # in float64 and rounding after differs (58.1f // 0.1)
+            a, b = [np.float32(v) if isinstance(v, np.float64) else v
+                    for v in (a, b)]
         r = ir.BINOPS[e.op](a, b)
         return _as_dtype(r, e.dtype)
     if isinstance(e, ir.Un):

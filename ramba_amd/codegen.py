@@ -405,8 +405,8 @@ class LaneEmitter:
             return self.fresh(ct, f"(({ct})({a})) / (({ct})({b}))")
         if op == "floordiv":
             if np.dtype(e.dtype).kind == "f":
-                return self.fresh(
-                    ct, f"floor{sfx}((({ct})({a})) / (({ct})({b})))")
+                return self.fresh(ct, f"rt_ffloordiv{sfx}(({ct})({a}), "
+                                      f"({ct})({b}))")
             return self.fresh(ct, f"rt_fdiv((long long)({a}), "
                                   f"(long long)({b}))")
         if op == "mod":
@@ -464,21 +464,59 @@ typedef __attribute__((ext_vector_type(4))) unsigned char b4_t;
 typedef __attribute__((ext_vector_type(2))) signed char c2_t;
 typedef __attribute__((ext_vector_type(4))) signed char c4_t;
 
+// Integer // and %: NumPy returns 0 for a zero divisor, and INT64_MIN // -1
+// wraps to INT64_MIN (remainder 0); both are undefined for C++ '/' and '%',
+// so they are answered before the division is evaluated.
 __device__ __forceinline__ i64 rt_fdiv(i64 a, i64 b) {
+    if (b == 0) return 0;
+    if (b == -1) return (i64)(0ULL - (u64)a);
     i64 q = a / b, r = a % b;
     return (r != 0 && ((r < 0) != (b < 0))) ? q - 1 : q;
 }
 __device__ __forceinline__ i64 rt_imod(i64 a, i64 b) {
+    if (b == 0 || b == -1) return 0;
     i64 r = a % b;
     return (r != 0 && ((r < 0) != (b < 0))) ? r + b : r;
 }
+// Float %: Python-style remainder (sign of b); an exact zero takes b's sign
+// (NumPy npy_divmod).
 __device__ __forceinline__ double rt_fmod(double a, double b) {
     double r = fmod(a, b);
-    return (r != 0.0 && ((r < 0.0) != (b < 0.0))) ? r + b : r;
+    if (r == 0.0) return __builtin_copysign(0.0, b);
+    return ((r < 0.0) != (b < 0.0)) ? r + b : r;
 }
 __device__ __forceinline__ float rt_fmodf(float a, float b) {
     float r = fmodf(a, b);
-    return (r != 0.0f && ((r < 0.0f) != (b < 0.0f))) ? r + b : r;
+    if (r == 0.0f) return __builtin_copysignf(0.0f, b);
+    return ((r < 0.0f) != (b < 0.0f)) ? r + b : r;
+}
+// Float //: NumPy's npy_divmod quotient, NOT floor(a / b) -- the rounded
+// a / b can land on the next integer (1.0 / 0.1 rounds to 10.0 although
+// 0.1 is above 1/10, so 1.0 // 0.1 is 9).  The quotient is derived from the
+// exact fmod remainder instead.
+__device__ __forceinline__ double rt_ffloordiv(double a, double b) {
+    if (b == 0.0) return a / b;
+    double mod = fmod(a, b);
+    double div = (a - mod) / b;
+    if (mod != 0.0 && ((b < 0.0) != (mod < 0.0))) div -= 1.0;
+    if (div != 0.0) {
+        double fl = floor(div);
+        if (div - fl > 0.5) fl += 1.0;
+        return fl;
+    }
+    return __builtin_copysign(0.0, a / b);
+}
+__device__ __forceinline__ float rt_ffloordivf(float a, float b) {
+    if (b == 0.0f) return a / b;
+    float mod = fmodf(a, b);
+    float div = (a - mod) / b;
+    if (mod != 0.0f && ((b < 0.0f) != (mod < 0.0f))) div -= 1.0f;
+    if (div != 0.0f) {
+        float fl = floorf(div);
+        if (div - fl > 0.5f) fl += 1.0f;
+        return fl;
+    }
+    return __builtin_copysignf(0.0f, a / b);
 }
 __device__ __forceinline__ i64 rt_ipow(i64 b, i64 e) {
     i64 r = 1;
@@ -491,8 +529,12 @@ __device__ __forceinline__ i64 rt_ipow(i64 b, i64 e) {
 // __kernel_sin/__kernel_cos minimax polynomials; falls back to ocml
 // sincos (full Payne-Hanek) outside the fast range.  ~45 fp64 ops for
 // BOTH results vs ~2x that for two ocml calls — the hot chain is at the
-// HBM/VALU crossover (SURVEY §7), so this is a throughput lever, and it
-// stays well inside the 1e-12 parity tolerance (abs err ~1 ulp).
+// HBM/VALU crossover (SURVEY §7), so this is a throughput lever.
+// Accuracy: within 1 spacing of the correctly rounded sin and cos on the
+// fast path, the doubles nearest to k*pi/2 included (all three reduction
+// stages), NaN / inf / signed zero as IEEE -- measured against mpmath
+// fixtures on the host (tests/test_preamble_host.py) and on the GPU
+// (tests/test_gpu_numeric_edges.py; table in DESIGN.md §6).
 __device__ __forceinline__ void rt_sincos(double x, double *sr, double *cr) {
     double ax = __builtin_fabs(x);
     if (!(ax < 1.0e6)) { sincos(x, sr, cr); return; }
@@ -501,7 +543,9 @@ __device__ __forceinline__ void rt_sincos(double x, double *sr, double *cr) {
     const double pio2_1t = 6.07710050650619224932e-11;
     const double pio2_2 = 6.07710050630396597660e-11;
     const double pio2_2t = 2.02226624879595063154e-21;
-    double fn = __builtin_rint(x * invpio2);
+    // + 0.0 turns rint's -0.0 (x == -0.0) into +0.0, so r below keeps x's
+    // sign and sin(-0.0) is -0.0
+    double fn = __builtin_rint(x * invpio2) + 0.0;
     int n = (int)fn;
     // fn*pio2_1 is exact while |fn| < 2^20 (pio2_1 carries 33 bits), so
     // y0+y1 ~ x - fn*pi/2 with ~1e-20 absolute error -- far inside the

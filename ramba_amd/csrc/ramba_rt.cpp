@@ -311,8 +311,11 @@ __global__ __launch_bounds__(256) void box_combine_kernel(
         T s = src[so], d0 = dst[dofs];
         if (OP == 0) dst[dofs] = d0 + s;
         else if (OP == 1) dst[dofs] = d0 * s;
-        else if (OP == 2) dst[dofs] = s < d0 ? s : d0;
-        else if (OP == 3) dst[dofs] = s > d0 ? s : d0;
+        // NaN-propagating min/max (NumPy semantics): a NaN in s loses
+        // every comparison, so take it explicitly; a NaN in d0 stays.
+        // s != s is constant-false for the integer instantiations.
+        else if (OP == 2) dst[dofs] = (s < d0 || s != s) ? s : d0;
+        else if (OP == 3) dst[dofs] = (s > d0 || s != s) ? s : d0;
         else if (OP == 4) dst[dofs] = (d0 != (T)0 && s != (T)0) ? (T)1 : (T)0;
         else dst[dofs] = (d0 != (T)0 || s != (T)0) ? (T)1 : (T)0;
     }
@@ -501,7 +504,11 @@ __global__ __launch_bounds__(256) void cumsum_k2(T *__restrict__ bsums,
     __syncthreads();
     T wbase = (T)0;
     for (int w = 0; w < wid; ++w) wbase += wsum[w];
-    T excl = wbase + x - s;   // exclusive prefix of this thread's range
+    // exclusive prefix of this thread's range: the lane below's inclusive
+    // value, NOT x - s (a NaN or inf in s would poison the prefix of the
+    // elements BEFORE it: inf - inf and nan - nan are nan)
+    T below = __shfl_up(x, 1, 64);
+    T excl = wbase + (lane > 0 ? below : (T)0);
     // rewrite this thread's range as exclusive prefixes
     T run = excl;
     for (int64_t i = lo; i < hi; ++i) {
@@ -558,7 +565,10 @@ __global__ __launch_bounds__(256) void cumsum_k3(const T *__restrict__ in,
         __syncthreads();
         T wbase = (T)0;
         for (int w = 0; w < wid; ++w) wbase += wsum[w];
-        T run = base + bsums[blk] + wbase + x - s;
+        // exclusive thread prefix from the lane below (x - s would turn a
+        // NaN/inf in this thread's items into NaN for the items before it)
+        T below = __shfl_up(x, 1, 64);
+        T run = base + bsums[blk] + wbase + (lane > 0 ? below : (T)0);
         for (int j = 0; j < SCAN_ITEMS; ++j) {
             if (l0 + j < lmax) {
                 run += lds[LIDX(l0 + j)];
@@ -654,7 +664,8 @@ __global__ __launch_bounds__(256) void cumsum_lookback(
         __syncthreads();
         T wbase = (T)0;
         for (int w = 0; w < wid; ++w) wbase += wsum[w];
-        T thread_excl = wbase + x - s;
+        T below = __shfl_up(x, 1, 64);
+        T thread_excl = wbase + (lane > 0 ? below : (T)0);
         T block_total = (T)0;
         for (int w = 0; w < 4; ++w) block_total += wsum[w];
         // publish aggregate; wave 0 then resolves the exclusive prefix by
