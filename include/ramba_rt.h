@@ -143,6 +143,53 @@ int rt_take_regime(const void *dst, const void *src, int nd_inner,
                    const int64_t *dst_strides, int64_t src_row_stride,
                    int64_t dst_row_stride, int elemsize);
 
+/* argmax / argmin / nanargmax / nanargmin — (value, index) pair reductions
+ * (the reference lists them as to-do, ramba/ramba.py:10288).  One pass over
+ * a strided box of 1..4 axes at `in + in_off` (offset and strides in
+ * elements); every merge uses rt_arg_better (include/ramba_argcmp.h).
+ * dtype: 0=f64 1=f32 2=i64 3=i32 4=i16 5=i8 6=u8 (bool).  Reported indices
+ * are idx0 + sum_d coord_d * mult_d; -1 = no candidate (skipna, all NaN).
+ * mult must make the index grow with C order over the box (the C strides
+ * of an enclosing shape, or 1 on the reduced axis): threads rely on it.
+ * nd, extents (>= 1), the dtype code and pointers are validated before any
+ * launch; a bad argument returns nonzero.
+ *
+ * rt_arg_flat: all axes -> out_val[1], out_idx[1] (device).  scratch_vals /
+ * scratch_idx hold rt_arg_grid_cap() pairs (8 bytes each side per pair).
+ * Stage 1 runs at most rt_arg_grid_cap() blocks of 256 lanes, each lane
+ * taking one load unit per trip, two trips per loop pass; a unit is 16
+ * bytes when rt_arg_flat_regime() is 1, else one element.
+ *
+ * rt_arg_axis: one axis -> out_vals / out_idx, dense C order over the kept
+ * axes; mult is 1 on `axis`.  axis == nd-1: one wave per line (16-byte
+ * loads when the axis stride is 1 and every line is aligned).  Otherwise
+ * one thread per output element, or, with nchunks > 1, per (chunk, output)
+ * into part_vals / part_idx [nchunks * nout] followed by a pair reduce.
+ *
+ * rt_arg_combine_box: dst(val, idx) = better(dst, src) over a box; the
+ * destination value and index arrays have their own strides and offsets. */
+int rt_arg_grid_cap(void);
+int rt_arg_flat_regime(const void *in, int64_t in_off, int nd,
+                       const int64_t *shape, const int64_t *strides,
+                       int dtype);
+int rt_arg_flat(uintptr_t stream, const void *in, int64_t in_off, int nd,
+                const int64_t *shape, const int64_t *strides,
+                const int64_t *mult, int64_t idx0, int dtype, int is_max,
+                int skipna, void *scratch_vals, void *scratch_idx,
+                void *out_val, void *out_idx);
+int rt_arg_axis(uintptr_t stream, const void *in, int64_t in_off, int nd,
+                const int64_t *shape, const int64_t *strides, int axis,
+                int64_t idx0, int dtype, int is_max, int skipna,
+                int64_t nchunks, void *part_vals, void *part_idx,
+                void *out_vals, void *out_idx);
+int rt_arg_combine_box(uintptr_t stream, void *dst_vals, void *dst_idx,
+                       const void *src_vals, const void *src_idx, int nd,
+                       const int64_t *shape, const int64_t *dst_val_strides,
+                       const int64_t *dst_idx_strides,
+                       const int64_t *src_strides, int64_t dst_val_off,
+                       int64_t dst_idx_off, int dtype, int is_max,
+                       int skipna);
+
 int rt_stream_sync(uintptr_t stream);
 int rt_device_sync(void);
 

@@ -1842,3 +1842,699 @@ extern "C" int rt_take_rows(uintptr_t stream, void *dst, const void *src,
                                               dst_rows, g, re, regime, bad);
     }
 }
+
+// ---------------------------------------------------------------------------
+// argmax / argmin / nanargmax / nanargmin: (value, index) pair reductions.
+// The reference only lists these as to-do (ramba/ramba.py:10288).
+//
+// Every kernel carries a pair through its tree and merges with the one
+// comparator of include/ramba_argcmp.h.  An element's index is always
+// derived from its coordinates in the box —
+//     idx = idx0 + sum_d coord_d * mult_d
+// (mult = 1 on the reduced axis for an axis reduction, the view shape's C
+// strides for the flat one; idx0 places the rank's box in the global view)
+// — never from a running counter, so a reversed, stepped or transposed
+// operand reports view order.  No atomics: the pair order is total, the
+// result is the same pair whatever the grouping.  No kernel forms an
+// address from data; extents, strides and the dtype code are validated on
+// the host side of each entry before anything is launched.
+// ---------------------------------------------------------------------------
+
+#include "../../include/ramba_argcmp.h"
+
+namespace {
+
+// blocks of the flat stage 1 (256 CUs x 8 blocks, the memory-bound grid
+// cap); each block leaves one pair for stage 2
+enum { ARG_GRID_CAP = 2048 };
+
+const int ARG_ESZ[7] = {8, 4, 8, 4, 2, 1, 1};
+
+template <typename T>
+__device__ __forceinline__ T arg_shfl(T v, int d) {
+    if constexpr (sizeof(T) == 8) {
+        long long b;
+        __builtin_memcpy(&b, &v, 8);
+        b = __shfl_down(b, d);
+        T r;
+        __builtin_memcpy(&r, &b, 8);
+        return r;
+    } else if constexpr (sizeof(T) == 4) {
+        int b;
+        __builtin_memcpy(&b, &v, 4);
+        b = __shfl_down(b, d);
+        T r;
+        __builtin_memcpy(&r, &b, 4);
+        return r;
+    } else {
+        return (T)__shfl_down((int)v, d);
+    }
+}
+
+template <typename T>
+__device__ __forceinline__ void arg_take(T &bv, int64_t &bi, T v, int64_t i,
+                                         int mx, int sk) {
+    if (rt_arg_better<T>(v, i, bv, bi, mx, sk)) {
+        bv = v;
+        bi = i;
+    }
+}
+
+// all 64 lanes take part; the wave's pair ends in lane 0
+template <typename T>
+__device__ __forceinline__ void arg_wave_reduce(T &bv, int64_t &bi, int mx,
+                                                int sk) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        const T ov = arg_shfl<T>(bv, d);
+        const int64_t oi = arg_shfl<int64_t>(bi, d);
+        arg_take<T>(bv, bi, ov, oi, mx, sk);
+    }
+}
+
+// 256 threads = 4 waves: shuffles, then an LDS hand-off; the block's pair
+// ends in thread 0
+template <typename T>
+__device__ __forceinline__ void arg_block_reduce(T &bv, int64_t &bi, int mx,
+                                                 int sk) {
+    __shared__ T sv[4];
+    __shared__ int64_t si[4];
+    arg_wave_reduce<T>(bv, bi, mx, sk);
+    if ((threadIdx.x & 63) == 0) {
+        sv[threadIdx.x >> 6] = bv;
+        si[threadIdx.x >> 6] = bi;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int k = 1; k < 4; ++k) arg_take<T>(bv, bi, sv[k], si[k], mx, sk);
+}
+
+// -- flat (all axes) ---------------------------------------------------------
+
+struct ArgFlatArgs {
+    int64_t nunits;          // load units in the box
+    int64_t shp[4];          // extents, right-aligned; innermost in units
+    int64_t str[4];          // strides in load units
+    int64_t mult[4];         // index multiplier per ELEMENT coordinate
+    int64_t idx0;
+    int64_t tail0, tailn;    // 1-D 16-byte path: elements past the last unit
+    int nd, is_max, skipna;
+};
+
+template <typename T, typename L>
+__device__ __forceinline__ void arg_flat_addr(const ArgFlatArgs &a, int64_t u,
+                                              int64_t &off, int64_t &ib) {
+    constexpr int PER = sizeof(L) / sizeof(T);
+    if (a.nd == 1) {
+        off = u * a.str[3];
+        ib = a.idx0 + u * PER * a.mult[3];
+        return;
+    }
+    uint64_t rem = (uint64_t)u;
+    off = 0;
+    ib = a.idx0;
+#pragma unroll
+    for (int d = 3; d >= 0; --d) {
+        const uint64_t q = rem / (uint64_t)a.shp[d];
+        const int64_t c = (int64_t)(rem - q * (uint64_t)a.shp[d]);
+        rem = q;
+        off += c * a.str[d];
+        ib += c * (d == 3 ? PER : 1) * a.mult[d];
+    }
+}
+
+// In-thread accumulate of one load unit whose elements sit at indices ib,
+// ib + step, ...: every thread walks its elements in increasing index
+// order, so the comparator's LATER form applies (strictly better only) and
+// the 64-bit index is formed only when an element is taken.  MX / SK are
+// compile-time so the test folds.
+template <typename T, typename L, int MX, int SK>
+__device__ __forceinline__ void arg_unit_acc(const L &unit, int64_t ib,
+                                             int64_t step, T &bv,
+                                             int64_t &bi) {
+    constexpr int PER = sizeof(L) / sizeof(T);
+    T e[PER];
+    __builtin_memcpy(e, &unit, sizeof(L));
+#pragma unroll
+    for (int j = 0; j < PER; ++j)
+        if (rt_arg_better<T, true>(e[j], 0, bv, bi, MX, SK)) {
+            bv = e[j];
+            bi = ib + j * step;
+        }
+}
+
+// run BODY<MX, SK> for the launch's (uniform) is_max / skipna
+#define ARG_FLAGS(mx, sk, BODY)                                            \
+    do {                                                                   \
+        if (mx) {                                                          \
+            if (sk) BODY(1, 1); else BODY(1, 0);                           \
+        } else {                                                           \
+            if (sk) BODY(0, 1); else BODY(0, 0);                           \
+        }                                                                  \
+    } while (0)
+
+template <typename T, typename L, int MX, int SK>
+__device__ __forceinline__ void arg_flat_walk(const T *__restrict__ in,
+                                              const ArgFlatArgs &a, T &bv,
+                                              int64_t &bi) {
+    const L *src = reinterpret_cast<const L *>(in);
+    const int64_t S = (int64_t)gridDim.x * 256;
+    const int64_t step = a.mult[3];
+    int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    for (; u + S < a.nunits; u += 2 * S) {
+        int64_t o0, i0, o1, i1;
+        arg_flat_addr<T, L>(a, u, o0, i0);
+        arg_flat_addr<T, L>(a, u + S, o1, i1);
+        const L x0 = src[o0];
+        const L x1 = src[o1];
+        arg_unit_acc<T, L, MX, SK>(x0, i0, step, bv, bi);
+        arg_unit_acc<T, L, MX, SK>(x1, i1, step, bv, bi);
+    }
+    if (u < a.nunits) {
+        int64_t o0, i0;
+        arg_flat_addr<T, L>(a, u, o0, i0);
+        const L x0 = src[o0];
+        arg_unit_acc<T, L, MX, SK>(x0, i0, step, bv, bi);
+    }
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t < a.tailn)
+        arg_unit_acc<T, T, MX, SK>(in[a.tail0 + t],
+                                   a.idx0 + (a.tail0 + t) * step, step, bv,
+                                   bi);
+}
+
+// Stage 1: grid-stride over the box's load units (L = uint4 when the
+// innermost stride is 1 and everything is 16-byte aligned, else one
+// element), two loads in flight per lane; one pair per block.
+template <typename T, typename L>
+__global__ __launch_bounds__(256) void arg_flat_s1(const T *__restrict__ in,
+                                                   ArgFlatArgs a,
+                                                   T *__restrict__ pv,
+                                                   int64_t *__restrict__ pi) {
+    T bv = T(0);
+    int64_t bi = -1;
+#define BODY(MX, SK) arg_flat_walk<T, L, MX, SK>(in, a, bv, bi)
+    ARG_FLAGS(a.is_max, a.skipna, BODY);
+#undef BODY
+    arg_block_reduce<T>(bv, bi, a.is_max, a.skipna);
+    if (threadIdx.x == 0) {
+        pv[blockIdx.x] = bv;
+        pi[blockIdx.x] = bi;
+    }
+}
+
+// Stage 2: one block reduces the per-block pairs into the output pair
+template <typename T>
+__global__ __launch_bounds__(256) void arg_flat_s2(
+    const T *__restrict__ pv, const int64_t *__restrict__ pi, int n,
+    T *__restrict__ ov, int64_t *__restrict__ oi, int mx, int sk) {
+    T bv = T(0);
+    int64_t bi = -1;
+    for (int k = threadIdx.x; k < n; k += 256)
+        arg_take<T>(bv, bi, pv[k], pi[k], mx, sk);
+    arg_block_reduce<T>(bv, bi, mx, sk);
+    if (threadIdx.x == 0) {
+        ov[0] = bv;
+        oi[0] = bi;
+    }
+}
+
+// 16-byte loads iff the innermost stride is 1, the first element is
+// 16-byte aligned and, beyond 1-D, the innermost extent and every outer
+// stride are whole units (1-D keeps a scalar tail instead)
+bool arg_flat_vec(const void *in, int64_t in_off, int nd,
+                  const int64_t *shape, const int64_t *strides, int es) {
+    const int64_t per = 16 / es;
+    if (strides[nd - 1] != 1) return false;
+    if ((reinterpret_cast<uintptr_t>(in) + (uint64_t)(in_off * es)) % 16)
+        return false;
+    if (nd == 1) return shape[0] >= per;
+    if (shape[nd - 1] % per) return false;
+    for (int d = 0; d < nd - 1; ++d)
+        if (strides[d] % per) return false;
+    return true;
+}
+
+int arg_validate(const char *who, const void *in, int nd,
+                 const int64_t *shape, const int64_t *strides, int dtype,
+                 int64_t *n_out) {
+    if (dtype < 0 || dtype > 6) {
+        set_error(std::string(who) + ": bad dtype");
+        return 1;
+    }
+    if (nd < 1 || nd > 4) {
+        set_error(std::string(who) + ": nd out of range");
+        return 1;
+    }
+    if (!in || !shape || !strides) {
+        set_error(std::string(who) + ": NULL argument");
+        return 1;
+    }
+    int64_t n = 1;
+    for (int d = 0; d < nd; ++d) {
+        if (shape[d] < 1 || shape[d] >= (1LL << 40)) {
+            set_error(std::string(who) + ": extent out of range");
+            return 1;
+        }
+        if (n > (1LL << 46) / shape[d]) {
+            set_error(std::string(who) + ": box too large");
+            return 1;
+        }
+        n *= shape[d];
+    }
+    *n_out = n;
+    return 0;
+}
+
+int arg_launch_status(const char *who) {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        set_error(std::string(who) + " launch: " + hipGetErrorString(e));
+        return 1;
+    }
+    return 0;
+}
+
+template <typename T>
+int arg_flat_launch(uintptr_t stream, const void *in, int64_t in_off, int nd,
+                    const int64_t *shape, const int64_t *strides,
+                    const int64_t *mult, int64_t idx0, int64_t n, bool vec,
+                    int is_max, int skipna, void *sv, void *si, void *ov,
+                    void *oi) {
+    const int64_t per = vec ? 16 / (int64_t)sizeof(T) : 1;
+    ArgFlatArgs a;
+    a.nd = nd;
+    a.is_max = is_max;
+    a.skipna = skipna;
+    a.idx0 = idx0;
+    a.tail0 = a.tailn = 0;
+    for (int d = 0; d < 4; ++d) {
+        const int s = d - (4 - nd);
+        a.shp[d] = s >= 0 ? shape[s] : 1;
+        a.str[d] = s >= 0 ? strides[s] : 0;
+        a.mult[d] = s >= 0 ? mult[s] : 0;
+        if (vec && d < 3) a.str[d] /= per;
+    }
+    if (vec) {
+        a.tail0 = (a.shp[3] / per) * per;
+        a.tailn = a.shp[3] - a.tail0;     // nonzero only when nd == 1
+        a.shp[3] /= per;
+        a.nunits = n / shape[nd - 1] * a.shp[3];
+    } else {
+        a.nunits = n;
+    }
+    int64_t blocks = (a.nunits + 255) / 256;
+    if (blocks > ARG_GRID_CAP) blocks = ARG_GRID_CAP;
+    if (blocks < 1) blocks = 1;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const T *src = static_cast<const T *>(in) + in_off;
+    if (vec)
+        hipLaunchKernelGGL((arg_flat_s1<T, uint4>), dim3((unsigned)blocks),
+                           dim3(256), 0, st, src, a, static_cast<T *>(sv),
+                           static_cast<int64_t *>(si));
+    else
+        hipLaunchKernelGGL((arg_flat_s1<T, T>), dim3((unsigned)blocks),
+                           dim3(256), 0, st, src, a, static_cast<T *>(sv),
+                           static_cast<int64_t *>(si));
+    if (arg_launch_status("rt_arg_flat(1)")) return 1;
+    hipLaunchKernelGGL((arg_flat_s2<T>), dim3(1), dim3(256), 0, st,
+                       static_cast<const T *>(sv),
+                       static_cast<const int64_t *>(si), (int)blocks,
+                       static_cast<T *>(ov), static_cast<int64_t *>(oi),
+                       is_max, skipna);
+    return arg_launch_status("rt_arg_flat(2)");
+}
+
+// -- one axis ----------------------------------------------------------------
+
+struct ArgAxisArgs {
+    int64_t nout;
+    int64_t oshp[3], ostr[3];   // kept axes, right-aligned: extent, in-stride
+    int64_t K, kstr, idx0;      // reduced axis
+    int64_t C, clen;            // chunks of the reduced axis (thread regime)
+    int is_max, skipna;
+};
+
+__device__ __forceinline__ int64_t arg_line_off(const ArgAxisArgs &a,
+                                                int64_t o) {
+    uint64_t rem = (uint64_t)o;
+    int64_t off = 0;
+#pragma unroll
+    for (int d = 2; d >= 0; --d) {
+        const uint64_t q = rem / (uint64_t)a.oshp[d];
+        off += (int64_t)(rem - q * (uint64_t)a.oshp[d]) * a.ostr[d];
+        rem = q;
+    }
+    return off;
+}
+
+// reduced axis innermost: one wave per line, lanes stride the line in load
+// units, four loads in flight per lane.  L = uint4 (the host checked: axis
+// stride 1, every line 16-byte aligned) leaves the K % PER last elements
+// to a scalar tail.
+template <typename T, typename L, int MX, int SK>
+__device__ __forceinline__ void arg_line_walk(const T *__restrict__ line,
+                                              const ArgAxisArgs &a, int lane,
+                                              T &bv, int64_t &bi) {
+    constexpr int PER = sizeof(L) / sizeof(T);
+    const L *src = reinterpret_cast<const L *>(line);
+    const int64_t units = a.K / PER;
+    const int64_t us = PER > 1 ? 1 : a.kstr;
+    int64_t u = lane;
+    for (; u + 192 < units; u += 256) {
+        const L x0 = src[u * us];
+        const L x1 = src[(u + 64) * us];
+        const L x2 = src[(u + 128) * us];
+        const L x3 = src[(u + 192) * us];
+        arg_unit_acc<T, L, MX, SK>(x0, a.idx0 + u * PER, 1, bv, bi);
+        arg_unit_acc<T, L, MX, SK>(x1, a.idx0 + (u + 64) * PER, 1, bv, bi);
+        arg_unit_acc<T, L, MX, SK>(x2, a.idx0 + (u + 128) * PER, 1, bv, bi);
+        arg_unit_acc<T, L, MX, SK>(x3, a.idx0 + (u + 192) * PER, 1, bv, bi);
+    }
+    for (; u < units; u += 64) {
+        const L x0 = src[u * us];
+        arg_unit_acc<T, L, MX, SK>(x0, a.idx0 + u * PER, 1, bv, bi);
+    }
+    if (PER > 1) {
+        const int64_t k = units * PER + lane;
+        if (k < a.K)
+            arg_unit_acc<T, T, MX, SK>(line[k], a.idx0 + k, 1, bv, bi);
+    }
+}
+
+// one chunk [k, k1) of one line, by one thread
+template <typename T, int MX, int SK>
+__device__ __forceinline__ void arg_chunk_walk(const T *__restrict__ line,
+                                               const ArgAxisArgs &a,
+                                               int64_t k, int64_t k1, T &bv,
+                                               int64_t &bi) {
+    for (; k + 3 < k1; k += 4) {            // four loads in flight
+        const T v0 = line[k * a.kstr];
+        const T v1 = line[(k + 1) * a.kstr];
+        const T v2 = line[(k + 2) * a.kstr];
+        const T v3 = line[(k + 3) * a.kstr];
+        arg_unit_acc<T, T, MX, SK>(v0, a.idx0 + k, 1, bv, bi);
+        arg_unit_acc<T, T, MX, SK>(v1, a.idx0 + k + 1, 1, bv, bi);
+        arg_unit_acc<T, T, MX, SK>(v2, a.idx0 + k + 2, 1, bv, bi);
+        arg_unit_acc<T, T, MX, SK>(v3, a.idx0 + k + 3, 1, bv, bi);
+    }
+    for (; k < k1; ++k)
+        arg_unit_acc<T, T, MX, SK>(line[k * a.kstr], a.idx0 + k, 1, bv, bi);
+}
+
+template <typename T, typename L>
+__global__ __launch_bounds__(256) void arg_axis_wave(
+    const T *__restrict__ in, ArgAxisArgs a, T *__restrict__ ov,
+    int64_t *__restrict__ oi) {
+    const int lane = threadIdx.x & 63;
+    const int64_t nwaves = (int64_t)gridDim.x * 4;
+    for (int64_t o = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+         o < a.nout; o += nwaves) {
+        const T *line = in + arg_line_off(a, o);
+        T bv = T(0);
+        int64_t bi = -1;
+#define BODY(MX, SK) arg_line_walk<T, L, MX, SK>(line, a, lane, bv, bi)
+        ARG_FLAGS(a.is_max, a.skipna, BODY);
+#undef BODY
+        arg_wave_reduce<T>(bv, bi, a.is_max, a.skipna);
+        if (lane == 0) {
+            ov[o] = bv;
+            oi[o] = bi;
+        }
+    }
+}
+
+// reduced axis not innermost: one thread per (chunk, output element),
+// consecutive threads on consecutive outputs (coalesced); pair t goes to
+// ov/oi[t], t = chunk * nout + output.  C == 1 is the plain regime.
+template <typename T>
+__global__ __launch_bounds__(256) void arg_axis_thread(
+    const T *__restrict__ in, ArgAxisArgs a, T *__restrict__ ov,
+    int64_t *__restrict__ oi) {
+    const int64_t total = a.nout * a.C;
+    const int64_t S = (int64_t)gridDim.x * 256;
+    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total;
+         t += S) {
+        const int64_t c = t / a.nout, o = t - c * a.nout;
+        const int64_t off = arg_line_off(a, o);
+        int64_t k1 = (c + 1) * a.clen;
+        if (k1 > a.K) k1 = a.K;
+        T bv = T(0);
+        int64_t bi = -1;
+#define BODY(MX, SK)                                                       \
+    arg_chunk_walk<T, MX, SK>(in + off, a, c * a.clen, k1, bv, bi)
+        ARG_FLAGS(a.is_max, a.skipna, BODY);
+#undef BODY
+        ov[t] = bv;
+        oi[t] = bi;
+    }
+}
+
+// the chunks' pairs (C, nout) -> one pair per output element
+template <typename T>
+__global__ __launch_bounds__(256) void arg_pairs_reduce(
+    const T *__restrict__ pv, const int64_t *__restrict__ pi, int64_t C,
+    int64_t nout, T *__restrict__ ov, int64_t *__restrict__ oi, int mx,
+    int sk) {
+    const int64_t S = (int64_t)gridDim.x * 256;
+    for (int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x; o < nout;
+         o += S) {
+        T bv = T(0);
+        int64_t bi = -1;
+        for (int64_t c = 0; c < C; ++c)
+            arg_take<T>(bv, bi, pv[c * nout + o], pi[c * nout + o], mx, sk);
+        ov[o] = bv;
+        oi[o] = bi;
+    }
+}
+
+unsigned arg_blocks(int64_t threads) {
+    int64_t b = (threads + 255) / 256;
+    if (b > 4096) b = 4096;
+    if (b < 1) b = 1;
+    return (unsigned)b;
+}
+
+template <typename T>
+int arg_axis_launch(uintptr_t stream, const void *in, int64_t in_off,
+                    const ArgAxisArgs &a, bool wave, bool vec, void *pv,
+                    void *pi, void *ov, void *oi) {
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const T *src = static_cast<const T *>(in) + in_off;
+    T *outv = static_cast<T *>(ov);
+    int64_t *outi = static_cast<int64_t *>(oi);
+    if (wave) {
+        if (vec)
+            hipLaunchKernelGGL((arg_axis_wave<T, uint4>),
+                               dim3(arg_blocks(a.nout * 64)), dim3(256), 0,
+                               st, src, a, outv, outi);
+        else
+            hipLaunchKernelGGL((arg_axis_wave<T, T>),
+                               dim3(arg_blocks(a.nout * 64)), dim3(256), 0,
+                               st, src, a, outv, outi);
+        return arg_launch_status("rt_arg_axis(wave)");
+    }
+    if (a.C == 1) {
+        hipLaunchKernelGGL((arg_axis_thread<T>), dim3(arg_blocks(a.nout)),
+                           dim3(256), 0, st, src, a, outv, outi);
+        return arg_launch_status("rt_arg_axis(thread)");
+    }
+    hipLaunchKernelGGL((arg_axis_thread<T>), dim3(arg_blocks(a.nout * a.C)),
+                       dim3(256), 0, st, src, a, static_cast<T *>(pv),
+                       static_cast<int64_t *>(pi));
+    if (arg_launch_status("rt_arg_axis(chunks)")) return 1;
+    hipLaunchKernelGGL((arg_pairs_reduce<T>), dim3(arg_blocks(a.nout)),
+                       dim3(256), 0, st, static_cast<const T *>(pv),
+                       static_cast<const int64_t *>(pi), a.C, a.nout, outv,
+                       outi, a.is_max, a.skipna);
+    return arg_launch_status("rt_arg_axis(pairs)");
+}
+
+// -- pair combine (rt_combine_box for pairs) ----------------------------------
+
+struct ArgBoxArgs {
+    int64_t n;
+    int64_t shape[4], dvs[4], dis[4], ss[4];
+    int nd, is_max, skipna;
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void arg_combine_kernel(
+    T *__restrict__ dv, int64_t *__restrict__ di, const T *__restrict__ sv,
+    const int64_t *__restrict__ si, ArgBoxArgs a) {
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (; i < a.n; i += stride) {
+        int64_t rem = i, so = 0, vo = 0, io = 0;
+        for (int d = a.nd - 1; d >= 0; --d) {
+            const int64_t idx = rem % a.shape[d];
+            rem /= a.shape[d];
+            so += idx * a.ss[d];
+            vo += idx * a.dvs[d];
+            io += idx * a.dis[d];
+        }
+        const T v = sv[so];
+        const int64_t k = si[so];
+        if (rt_arg_better<T>(v, k, dv[vo], di[io], a.is_max, a.skipna)) {
+            dv[vo] = v;
+            di[io] = k;
+        }
+    }
+}
+
+template <typename T>
+int arg_combine_launch(uintptr_t stream, void *dv, void *di, const void *sv,
+                       const void *si, int64_t dv_off, int64_t di_off,
+                       const ArgBoxArgs &a) {
+    int64_t blocks = (a.n + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL((arg_combine_kernel<T>), dim3((unsigned)blocks),
+                       dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                       static_cast<T *>(dv) + dv_off,
+                       static_cast<int64_t *>(di) + di_off,
+                       static_cast<const T *>(sv),
+                       static_cast<const int64_t *>(si), a);
+    return arg_launch_status("rt_arg_combine_box");
+}
+
+#define ARG_DISPATCH(dtype, CALL)                                          \
+    switch (dtype) {                                                       \
+        case 0: return CALL(double);                                       \
+        case 1: return CALL(float);                                        \
+        case 2: return CALL(int64_t);                                      \
+        case 3: return CALL(int32_t);                                      \
+        case 4: return CALL(int16_t);                                      \
+        case 5: return CALL(int8_t);                                       \
+        default: return CALL(uint8_t);                                     \
+    }
+
+}  // namespace
+
+extern "C" int rt_arg_grid_cap(void) { return ARG_GRID_CAP; }
+
+extern "C" int rt_arg_flat_regime(const void *in, int64_t in_off, int nd,
+                                  const int64_t *shape,
+                                  const int64_t *strides, int dtype) {
+    int64_t n;
+    if (arg_validate("rt_arg_flat_regime", in, nd, shape, strides, dtype, &n))
+        return -1;
+    return arg_flat_vec(in, in_off, nd, shape, strides, ARG_ESZ[dtype]) ? 1
+                                                                        : 0;
+}
+
+extern "C" int rt_arg_flat(uintptr_t stream, const void *in, int64_t in_off,
+                           int nd, const int64_t *shape,
+                           const int64_t *strides, const int64_t *mult,
+                           int64_t idx0, int dtype, int is_max, int skipna,
+                           void *scratch_vals, void *scratch_idx,
+                           void *out_val, void *out_idx) {
+    int64_t n;
+    if (arg_validate("rt_arg_flat", in, nd, shape, strides, dtype, &n))
+        return 1;
+    if (!mult || !scratch_vals || !scratch_idx || !out_val || !out_idx) {
+        set_error("rt_arg_flat: NULL argument");
+        return 1;
+    }
+    const bool vec =
+        arg_flat_vec(in, in_off, nd, shape, strides, ARG_ESZ[dtype]);
+#define CALL(T)                                                            \
+    arg_flat_launch<T>(stream, in, in_off, nd, shape, strides, mult, idx0, \
+                       n, vec, is_max != 0, skipna != 0, scratch_vals,     \
+                       scratch_idx, out_val, out_idx)
+    ARG_DISPATCH(dtype, CALL)
+#undef CALL
+}
+
+extern "C" int rt_arg_axis(uintptr_t stream, const void *in, int64_t in_off,
+                           int nd, const int64_t *shape,
+                           const int64_t *strides, int axis, int64_t idx0,
+                           int dtype, int is_max, int skipna,
+                           int64_t nchunks, void *part_vals, void *part_idx,
+                           void *out_vals, void *out_idx) {
+    int64_t n;
+    if (arg_validate("rt_arg_axis", in, nd, shape, strides, dtype, &n))
+        return 1;
+    if (axis < 0 || axis >= nd) {
+        set_error("rt_arg_axis: axis out of range");
+        return 1;
+    }
+    if (!out_vals || !out_idx) {
+        set_error("rt_arg_axis: NULL output");
+        return 1;
+    }
+    const bool wave = axis == nd - 1;
+    if (nchunks < 1 || nchunks > shape[axis]
+        || (nchunks > 1 && (wave || !part_vals || !part_idx))) {
+        set_error("rt_arg_axis: bad chunking");
+        return 1;
+    }
+    ArgAxisArgs a;
+    a.K = shape[axis];
+    a.kstr = strides[axis];
+    a.idx0 = idx0;
+    a.C = nchunks;
+    a.clen = (a.K + nchunks - 1) / nchunks;
+    a.is_max = is_max != 0;
+    a.skipna = skipna != 0;
+    a.nout = n / a.K;
+    for (int d = 0; d < 3; ++d) {
+        a.oshp[d] = 1;
+        a.ostr[d] = 0;
+    }
+    int slot = 2;
+    for (int d = nd - 1; d >= 0; --d) {
+        if (d == axis) continue;
+        a.oshp[slot] = shape[d];
+        a.ostr[slot] = strides[d];
+        --slot;
+    }
+    // wave regime with 16-byte loads: axis stride 1 and every line start
+    // (base + any combination of kept-axis strides) 16-byte aligned
+    const int es = ARG_ESZ[dtype];
+    bool vec = wave && strides[axis] == 1 && shape[axis] >= 16 / es
+        && (reinterpret_cast<uintptr_t>(in) + (uint64_t)(in_off * es)) % 16
+               == 0;
+    for (int d = 0; vec && d < nd - 1; ++d)
+        vec = (strides[d] * es) % 16 == 0;
+#define CALL(T)                                                            \
+    arg_axis_launch<T>(stream, in, in_off, a, wave, vec, part_vals,        \
+                       part_idx, out_vals, out_idx)
+    ARG_DISPATCH(dtype, CALL)
+#undef CALL
+}
+
+extern "C" int rt_arg_combine_box(uintptr_t stream, void *dst_vals,
+                                  void *dst_idx, const void *src_vals,
+                                  const void *src_idx, int nd,
+                                  const int64_t *shape,
+                                  const int64_t *dst_val_strides,
+                                  const int64_t *dst_idx_strides,
+                                  const int64_t *src_strides,
+                                  int64_t dst_val_off, int64_t dst_idx_off,
+                                  int dtype, int is_max, int skipna) {
+    int64_t n;
+    if (arg_validate("rt_arg_combine_box", src_vals, nd, shape, src_strides,
+                     dtype, &n))
+        return 1;
+    if (!dst_vals || !dst_idx || !src_idx || !dst_val_strides
+        || !dst_idx_strides) {
+        set_error("rt_arg_combine_box: NULL argument");
+        return 1;
+    }
+    ArgBoxArgs a;
+    a.nd = nd;
+    a.n = n;
+    a.is_max = is_max != 0;
+    a.skipna = skipna != 0;
+    for (int d = 0; d < 4; ++d) {
+        a.shape[d] = d < nd ? shape[d] : 1;
+        a.dvs[d] = d < nd ? dst_val_strides[d] : 0;
+        a.dis[d] = d < nd ? dst_idx_strides[d] : 0;
+        a.ss[d] = d < nd ? src_strides[d] : 0;
+    }
+#define CALL(T)                                                            \
+    arg_combine_launch<T>(stream, dst_vals, dst_idx, src_vals, src_idx,    \
+                          dst_val_off, dst_idx_off, a)
+    ARG_DISPATCH(dtype, CALL)
+#undef CALL
+}

@@ -104,6 +104,18 @@ def _load_lib():
                                    ctypes.c_int, _p64, _p64, _p64,
                                    ctypes.c_int64, ctypes.c_int64,
                                    ctypes.c_int]
+    _vp, _i64, _int = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
+    lib.rt_arg_grid_cap.restype = ctypes.c_int
+    lib.rt_arg_flat_regime.argtypes = [_vp, _i64, _int, _p64, _p64, _int]
+    lib.rt_arg_flat.argtypes = [ctypes.c_size_t, _vp, _i64, _int, _p64,
+                                _p64, _p64, _i64, _int, _int, _int, _vp,
+                                _vp, _vp, _vp]
+    lib.rt_arg_axis.argtypes = [ctypes.c_size_t, _vp, _i64, _int, _p64,
+                                _p64, _int, _i64, _int, _int, _int, _i64,
+                                _vp, _vp, _vp, _vp]
+    lib.rt_arg_combine_box.argtypes = [ctypes.c_size_t, _vp, _vp, _vp, _vp,
+                                       _int, _p64, _p64, _p64, _p64, _i64,
+                                       _i64, _int, _int, _int]
     lib.rt_stream_sync.argtypes = [ctypes.c_size_t]
     return lib
 
@@ -1021,6 +1033,98 @@ HipBackend._check_take_bad = _hb_check_take_bad
 HipBackend.take_index = _hb_take_index
 HipBackend.gather_rows = _hb_gather_rows
 HipBackend.place_rows = _hb_place_rows
+
+
+# -- argmax / argmin pair reductions (runtime.arg_reduce_op) -----------------
+#
+# The two hooks of ramba_amd/argreduce.py on the rt_arg_* kernels.  The
+# operand is read in place through the view's strides; pairs stay on the
+# device as (values in the array's dtype, int64 indices).
+
+
+def _hb_arg_chunks(nd, axis, nout, K):
+    """Chunks of the reduced axis: the small-nout / long-K test of
+    _hb_axis_reduce_partial (one thread per output would starve the chip)."""
+    if axis != nd - 1 and nout < 65536 and K >= 2048:
+        return max(1, min((1 << 22) // max(nout, 1), (K + 255) // 256, 4096))
+    return 1
+
+
+def _hb_arg_reduce_partial(self, bd, rt, view, lb, axis, mult, idx0, kind,
+                           skipna):
+    d_, _, cstrides, pads = rt.shard_geometry(bd)
+    off0, strides = view.operand_addressing(lb[0], cstrides, d_[0], pads)
+    shape = box_shape(lb)
+    nd = len(shape)
+    cont = self._cont(bd)
+    tdt = self._tdt(bd.dtype)
+    i64 = self.torch.int64
+    dtc = _DT_ENUM[str(np.dtype(bd.dtype))]
+    is_max, skipna = int(kind == "max"), int(bool(skipna))
+
+    def new(shp, dt):
+        return self.torch.empty(shp, dtype=dt, device="cuda")
+
+    if axis is None:
+        cap = self.lib.rt_arg_grid_cap()
+        sv, si = new(cap, tdt), new(cap, i64)
+        ov, oi = new(1, tdt), new(1, i64)
+        self._check(self.lib.rt_arg_flat(
+            self._stream(), ctypes.c_void_p(cont.data_ptr()), int(off0), nd,
+            _i64arr(shape), _i64arr(strides), _i64arr(mult), int(idx0), dtc,
+            is_max, skipna, ctypes.c_void_p(sv.data_ptr()),
+            ctypes.c_void_p(si.data_ptr()), ctypes.c_void_p(ov.data_ptr()),
+            ctypes.c_void_p(oi.data_ptr())), "rt_arg_flat")
+        return ov, oi
+    kd = tuple(1 if d == axis else shape[d] for d in range(nd))
+    K = shape[axis]
+    nout = 1
+    for s in kd:
+        nout *= s
+    ov, oi = new(kd, tdt), new(kd, i64)
+    C = _hb_arg_chunks(nd, axis, nout, K)
+    pv = pi = None
+    if C > 1:
+        pv, pi = new(C * nout, tdt), new(C * nout, i64)
+    self._check(self.lib.rt_arg_axis(
+        self._stream(), ctypes.c_void_p(cont.data_ptr()), int(off0), nd,
+        _i64arr(shape), _i64arr(strides), int(axis), int(idx0), dtc, is_max,
+        skipna, C, ctypes.c_void_p(pv.data_ptr()) if C > 1 else None,
+        ctypes.c_void_p(pi.data_ptr()) if C > 1 else None,
+        ctypes.c_void_p(ov.data_ptr()), ctypes.c_void_p(oi.data_ptr())),
+        "rt_arg_axis")
+    return ov, oi
+
+
+def _hb_arg_combine_box(self, out_bd, rt, box, best, rel, src_vals, src_idx,
+                        kind, skipna):
+    shape = box_shape(box)
+    nd = len(shape)
+    di_off, cs = self._box_off(out_bd, rt, box)
+    bs = best.stride()
+    dv_off = sum(int(rel[0, i]) * bs[i] for i in range(nd))
+    src_vals, src_idx = src_vals.contiguous(), src_idx.contiguous()
+    self._check(self.lib.rt_arg_combine_box(
+        self._stream(), ctypes.c_void_p(best.data_ptr()),
+        ctypes.c_void_p(self._cont(out_bd).data_ptr()),
+        ctypes.c_void_p(src_vals.data_ptr()),
+        ctypes.c_void_p(src_idx.data_ptr()), nd, _i64arr(shape),
+        _i64arr(bs), _i64arr(cs), _i64arr(src_idx.stride()), int(dv_off),
+        int(di_off), self._arg_dtc(best), int(kind == "max"),
+        int(bool(skipna))), "rt_arg_combine_box")
+
+
+def _hb_arg_dtc(self, t):
+    """_DT_ENUM code of a value tensor (bool containers are uint8)."""
+    for npdt, tdt in TORCH_DTYPE.items():
+        if tdt == t.dtype and npdt != np.dtype(np.bool_):
+            return _DT_ENUM[str(npdt)]
+    raise TypeError(f"arg reduction: unsupported value dtype {t.dtype}")
+
+
+HipBackend.arg_reduce_partial = _hb_arg_reduce_partial
+HipBackend.arg_combine_box = _hb_arg_combine_box
+HipBackend._arg_dtc = _hb_arg_dtc
 
 
 # -- cross-stage fusion (staged/tiled kernel; ramba_amd/staged.py) -----------

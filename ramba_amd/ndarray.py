@@ -532,6 +532,68 @@ class ndarray:
     def any(self, axis=None, keepdims=False, **kw):
         return self._reduce("any", axis=axis, keepdims=keepdims)
 
+    # -- index reductions (the reference lists them as to-do,
+    #    ramba.py:10288): one pass carrying a (value, index) pair,
+    #    runtime.arg_reduce_op.  Sync points, like a[mask] and take. -------
+
+    def _arg_reduce(self, kind, skipna, axis=None, out=None, keepdims=False):
+        name = ("nanarg" if skipna else "arg") + kind
+        if out is not None:
+            raise NotImplementedError(f"{name}: out= is not supported")
+        nd = self.ndim
+        if axis is not None:
+            if isinstance(axis, (bool, np.bool_)) \
+                    or not isinstance(axis, (int, np.integer)):
+                raise TypeError(f"'{type(axis).__name__}' object cannot be "
+                                "interpreted as an integer")
+            axis = int(axis)
+            if not (-nd <= axis < nd):
+                raise np.exceptions.AxisError(axis, nd)
+            axis = axis + nd if axis < 0 else axis
+        if nd > 4:
+            raise NotImplementedError(
+                f"{name} supports arrays of up to 4 dimensions")
+        red = range(nd) if axis is None else (axis,)
+        if any(self.shape[i] == 0 for i in red):
+            raise ValueError(f"attempt to get arg{kind} of an empty sequence")
+        # integers and bools have no NaN: nanarg* is arg*
+        skipna = bool(skipna) and self.dtype.kind == "f"
+        kd_shape = tuple(1 if i in red else self.shape[i] for i in range(nd))
+        if axis is not None and any(s == 0 for s in kd_shape):
+            # zero extent on a kept axis: an empty result, not an error
+            res = zeros(kd_shape, dtype=np.int64)
+        else:
+            deferred.flush()
+            rt = deferred.get_runtime()
+            res = rt.arg_reduce_op(self, axis, kind, skipna)
+            if axis is None:
+                if res < 0:
+                    raise ValueError("All-NaN slice encountered")
+                res = np.int64(res)
+                if keepdims:
+                    return np.asarray(res).reshape((1,) * nd)
+                return res
+            res = ndarray(res, View.identity(kd_shape))
+            # an all-NaN line left -1: one fused min, the same on every rank
+            if skipna and int(res.min()) < 0:
+                raise ValueError("All-NaN slice encountered")
+        if not keepdims:
+            res = res[tuple(0 if i == axis else slice(None)
+                            for i in range(nd))]
+        return res
+
+    def argmax(self, axis=None, out=None, keepdims=False):
+        return self._arg_reduce("max", False, axis, out, keepdims)
+
+    def argmin(self, axis=None, out=None, keepdims=False):
+        return self._arg_reduce("min", False, axis, out, keepdims)
+
+    def nanargmax(self, axis=None, out=None, keepdims=False):
+        return self._arg_reduce("max", True, axis, out, keepdims)
+
+    def nanargmin(self, axis=None, out=None, keepdims=False):
+        return self._arg_reduce("min", True, axis, out, keepdims)
+
     def clip(self, lo=None, hi=None, **kw):
         """reference TestBasic clip (test_distributed_array.py)."""
         out = self
@@ -1295,6 +1357,27 @@ ndarray._ARRAY_FUNC.update({
     "shape": lambda a: a.shape,
     "ndim": lambda a: a.ndim,
     "size": lambda a: a.size,
+})
+
+
+def _module_arg_reduction(name):
+    def f(a, axis=None, out=None, *, keepdims=False):
+        if isinstance(a, ndarray):
+            return getattr(a, name)(axis=axis, out=out, keepdims=keepdims)
+        kw = {"keepdims": True} if keepdims else {}
+        return getattr(np, name)(a, axis=axis, out=out, **kw)
+    f.__name__ = name
+    return f
+
+
+argmax = _module_arg_reduction("argmax")
+argmin = _module_arg_reduction("argmin")
+nanargmax = _module_arg_reduction("nanargmax")
+nanargmin = _module_arg_reduction("nanargmin")
+
+ndarray._ARRAY_FUNC.update({
+    "argmax": argmax, "argmin": argmin,
+    "nanargmax": nanargmax, "nanargmin": nanargmin,
 })
 
 

@@ -1228,3 +1228,127 @@ def take_op(self, src_bd, idx_bd):
 
 
 Runtime.take_op = take_op
+
+# ---------------------------------------------------------------------------
+# argmax / argmin / nanargmax / nanargmin (the reference lists them as
+# to-do, ramba/ramba.py:10288).  A (value, index) pair is carried through
+# the local kernel tree and the cross-rank combine.  Every rank reports
+# GLOBAL indices,
+#     idx = sum_d (base_d + i_d) * mult_d
+# with base the start of the rank's box in view space and mult = 1 on the
+# reduced axis / 0 elsewhere, or the view shape's C strides for axis=None.
+# Pair p replaces pair q when p is strictly better (NaN beats a number
+# unless skipna; else > for max, < for min) or equally good with the lower
+# index; idx -1 means "nothing here" and always loses.  Indices being
+# global, that order is total: the merge is order-independent, hence
+# deterministic.  The structure follows reduce_axes_op.
+# ---------------------------------------------------------------------------
+
+def arg_reduce_op(self, arr, axis, kind, skipna):
+    """axis None: the global C-order flat index as an int (-1: skipna and
+    everything is NaN).  Otherwise the int64 keepdims result's bdarray,
+    holding -1 where skipna met an all-NaN line."""
+    from .shardview import exec_boxes as _eb
+    from . import argreduce as _ar
+    bd, v = arr.bdarray, arr.view
+    nd = v.ndim
+    hooks = _ar.hooks_for(self.backend)
+    if axis is None:
+        mult = [1] * nd
+        for d in range(nd - 2, -1, -1):
+            mult[d] = mult[d + 1] * v.shape[d + 1]
+        mult = tuple(mult)
+    else:
+        mult = tuple(1 if d == axis else 0 for d in range(nd))
+
+    lbs = _eb(v, bd.divisions)
+    lb = lbs[self.rank]
+    vals = idxs = None
+    if lb is not None:
+        idx0 = sum(int(lb[0, d]) * mult[d] for d in range(nd))
+        vals, idxs = hooks.arg_reduce_partial(bd, self, v, lb, axis, mult,
+                                              idx0, kind, skipna)
+
+    if axis is None:
+        # bool travels as uint8 (collectives have no bool)
+        wire = np.dtype(np.uint8) if bd.dtype == np.bool_ \
+            else np.dtype(bd.dtype)
+        if lb is None:
+            val, idx = np.zeros((), dtype=wire)[()], np.int64(-1)
+        else:
+            val = vals.cpu().numpy().reshape(-1).view(wire)[0]
+            idx = np.int64(idxs.cpu().numpy().reshape(-1)[0])
+        allv = self.backend.allgather_scalars(val, wire)
+        alli = self.backend.allgather_scalars(idx, np.dtype(np.int64))
+        bv, bi = np.asarray(allv[0], dtype=wire), np.int64(alli[0])
+        for r in range(1, len(allv)):
+            pv, pi = np.asarray(allv[r], dtype=wire), np.int64(alli[r])
+            if bool(_ar.better(pv, pi, bv, bi, kind, skipna)):
+                bv, bi = pv, pi
+        return int(bi)
+
+    kd_shape = tuple(1 if d == axis else v.shape[d] for d in range(nd))
+    out_dtype = np.dtype(np.int64)
+    out_bd = deferred.bdarray(kd_shape, out_dtype,
+                              default_divisions(self.world, kd_shape),
+                              default_border, flex=False)
+    self.backend.alloc_container(out_bd, self)
+    out_bd.constructed = True
+    self.backend.fill_container(out_bd, self, -1)
+    core = self.core_box(out_bd, self.rank)
+    # running best values, shaped like the rank's result core box; a slot's
+    # content counts only once its index is >= 0
+    best = self.backend.new_message_buffer(box_shape(core), bd.dtype) \
+        if core is not None else None
+
+    # combining exchange plan (deterministic on every rank)
+    axes = (axis,)
+    msgs = []
+    for r in range(self.world):
+        if lbs[r] is None:
+            continue
+        pb = _proj_box(lbs[r], axes)
+        for s in range(self.world):
+            part = box_intersect(pb, self.core_box(out_bd, s))
+            if part is not None:
+                msgs.append((s, r, part))
+    msgs.sort(key=lambda m: (m[0], m[1], tuple(m[2][0]), tuple(m[2][1])))
+
+    my_pb = _proj_box(lb, axes) if lb is not None else None
+
+    def mine(t, bx):
+        sl = tuple(slice(int(bx[0, i] - my_pb[0, i]),
+                         int(bx[1, i] - my_pb[0, i]) + 1) for i in range(nd))
+        return t[sl].contiguous()
+
+    vsends, isends, recvs, merges = [], [], [], []
+    for (dst, src, bx) in msgs:
+        if src == self.rank and dst == self.rank:
+            merges.append((bx, mine(vals, bx), mine(idxs, bx)))
+            continue
+        if src == self.rank:
+            vsends.append((dst, mine(vals, bx)))
+            isends.append((dst, mine(idxs, bx)))
+        if dst == self.rank:
+            recvs.append((src, bx,
+                          self.backend.new_message_buffer(box_shape(bx),
+                                                          bd.dtype),
+                          self.backend.new_message_buffer(box_shape(bx),
+                                                          out_dtype)))
+    # each message is a pair of dense buffers; one exchange per side keeps
+    # a single buffer per peer and exchange
+    if vsends or recvs:
+        self.backend.exchange(vsends, [(s, bv) for (s, _, bv, _) in recvs])
+        self.backend.exchange(isends, [(s, bi) for (s, _, _, bi) in recvs])
+    merges.extend((bx, bv, bi) for (_, bx, bv, bi) in recvs)
+    for (bx, sv, si) in merges:
+        rel = bx.copy()
+        rel[0] -= core[0]
+        rel[1] -= core[0]
+        hooks.arg_combine_box(out_bd, self, bx, best, rel, sv, si, kind,
+                              skipna)
+    self.backend.free_temps()
+    return out_bd
+
+
+Runtime.arg_reduce_op = arg_reduce_op

@@ -1,6 +1,7 @@
 """Timings for the round-1 extension kernels at streaming scale
-(axis cumsum / mask-getitem / reshape) and for the indexed row gather
-(`python tools/bench_extras.py take` runs that leg alone).  Not the judged
+(axis cumsum / mask-getitem / reshape), for the indexed row gather
+(`python tools/bench_extras.py take` runs that leg alone) and for the
+arg-reduction kernels (`... argreduce`, likewise).  Not the judged
 bench line — evidence for DESIGN.md §9's extra rows; run under rocprofv3
 --stats for the per-kernel summary committed to profiles/."""
 
@@ -116,10 +117,142 @@ def take_leg(repeats=5, inner=10):
         ra.sync()
 
 
+def argreduce_leg(repeats=5, inner=10, n_flat=1_000_000_000, n_side=30000):
+    """The arg-reduction kernels on one GPU, timed like the take leg
+    (`repeats` windows of `inner` launches, implementations alternating,
+    rt_event_*).  (a) flat argmax of an n_flat-element fp64 vector against
+    max() on the same array (same bytes: the floor), torch.argmax on the same
+    tensor, and the two-pass where/min composition; (b) argmax(axis=1) and
+    argmax(axis=0) of an (n_side, n_side) fp32 array against the
+    max(axis=...) kernel and torch.argmax(dim=...).  GB/s = array bytes /
+    time."""
+    import torch
+    from ramba_amd import deferred
+    from ramba_amd.shardview import exec_boxes
+    rt = deferred.get_runtime()
+    be = rt.backend
+    lib = be.lib
+    lib.rt_event_create.argtypes = [ctypes.POINTER(ctypes.c_void_p)]
+    lib.rt_event_record.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
+    lib.rt_event_elapsed.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.POINTER(ctypes.c_float)]
+    ev0, ev1 = ctypes.c_void_p(), ctypes.c_void_p()
+    be._check(lib.rt_event_create(ctypes.byref(ev0)), "rt_event_create")
+    be._check(lib.rt_event_create(ctypes.byref(ev1)), "rt_event_create")
+
+    def window(fn):
+        ms = ctypes.c_float()
+        be._check(lib.rt_event_record(ev0, be._stream()), "rt_event_record")
+        for _ in range(inner):
+            fn()
+        be._check(lib.rt_event_record(ev1, be._stream()), "rt_event_record")
+        be._check(lib.rt_event_elapsed(ev0, ev1, ctypes.byref(ms)),
+                  "rt_event_elapsed")
+        return ms.value / inner
+
+    def core(arr):
+        bd = arr.bdarray
+        _, _, _, pads = rt.shard_geometry(bd)
+        sl = tuple(slice(p, p + s) for p, s in zip(pads, bd.shape))
+        return be._cont(bd)[sl]
+
+    def addressing(arr):
+        bd, v = arr.bdarray, arr.view
+        lb = exec_boxes(v, bd.divisions)[rt.rank]
+        d_, _, cstr, pads = rt.shard_geometry(bd)
+        off0, strides = v.operand_addressing(lb[0], cstr, d_[0], pads)
+        return bd, v, lb, off0, strides
+
+    def run(name, nbytes, impls, check):
+        for fn in impls.values():
+            fn()                            # warm-up of every shape
+        torch.cuda.synchronize()
+        check()
+        times = {tag: [] for tag in impls}
+        for _ in range(repeats):            # alternate the implementations
+            for tag, fn in impls.items():
+                times[tag].append(window(fn))
+        rec = {"case": name, "bytes": nbytes, "repeats": repeats,
+               "launches_per_window": inner}
+        for tag, ts in times.items():
+            ts = sorted(ts)
+            rec[tag] = {"ms_median": round(ts[len(ts) // 2], 4),
+                        "ms_min": round(ts[0], 4),
+                        "ms_max": round(ts[-1], 4),
+                        "gbs_median": round(
+                            nbytes / (ts[len(ts) // 2] * 1e-3) / 1e9, 1)}
+        print("ARGREDUCE " + json.dumps(rec), flush=True)
+
+    # (a) flat
+    n = n_flat
+    a = ra.sin(ra.arange(n) * 1e-3)
+    ra.sync()
+    bd, v, lb, _, _ = addressing(a)
+    t_core = core(a)
+    j = ra.arange(n)
+
+    def flat_kernel():
+        return be.arg_reduce_partial(bd, rt, v, lb, None, (1,), 0, "max",
+                                     False)
+
+    def composed():
+        m = a.max()
+        hit = (a == m) | (ra.isnan(a) & bool(np.isnan(m)))
+        return ra.where(hit, j, n).min()
+
+    def check_flat():
+        want = int(torch.argmax(t_core))
+        assert int(flat_kernel()[1].cpu()[0]) == want
+        assert int(a.argmax()) == want and int(composed()) == want
+
+    run(f"argmax_flat_{n:.0e}_fp64".replace("+", ""), n * 8,
+        {"rt_arg_flat": flat_kernel, "argmax()": lambda: a.argmax(),
+         "max()": lambda: a.max(),
+         "torch.argmax": lambda: torch.argmax(t_core),
+         "where_min_composition": composed}, check_flat)
+    del a, j, t_core, bd, v, lb
+    ra.sync()
+
+    # (b) one axis
+    s = n_side
+    A = ra.fromfunction(lambda i, k: ((i * 7 + k * 13) % 1000) * 1.0,
+                        (s, s), dtype=np.float32)
+    ra.sync()
+    bd, v, lb, off0, strides = addressing(A)
+    T = core(A)
+    for axis in (1, 0):
+        mult = tuple(1 if d == axis else 0 for d in range(2))
+
+        def arg_kernel():
+            return be.arg_reduce_partial(bd, rt, v, lb, axis, mult, 0,
+                                         "max", False)
+
+        def max_kernel():
+            be.axis_reduce_partial(bd, off0, strides, lb, (axis,), "max",
+                                   bd.dtype)
+            be.free_temps()
+
+        def check_axis():
+            got = arg_kernel()[1].reshape(-1)
+            assert torch.equal(got, torch.argmax(T, dim=axis))
+
+        run(f"argmax_axis{axis}_{s}x{s}_fp32", s * s * 4,
+            {"rt_arg_axis": arg_kernel, "max(axis) kernel": max_kernel,
+             "torch.argmax": lambda: torch.argmax(T, dim=axis)}, check_axis)
+    del A, T
+    ra.sync()
+
+
 def main():
     ra.init()
     if sys.argv[1:] == ["take"]:
         take_leg()
+        print("done", flush=True)
+        return
+    if sys.argv[1:2] == ["argreduce"]:
+        # optional sizes for a quick look: argreduce N_FLAT N_SIDE
+        extra = [int(float(x)) for x in sys.argv[2:4]]
+        argreduce_leg(*([5, 10] + extra))
         print("done", flush=True)
         return
     n = 16384
@@ -148,6 +281,7 @@ def main():
           lambda: C.reshape(31250, 32000), m * 32)
     del A, B, Bf, C
     take_leg()
+    argreduce_leg()
     print("done", flush=True)
 
 
