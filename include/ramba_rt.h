@@ -62,8 +62,21 @@ int rt_launch(void *kernel, unsigned gx, unsigned gy, unsigned gz,
               unsigned bx, uintptr_t stream, const void *args,
               size_t argsize);
 
+/* Argument contract shared by rt_copy_box, rt_combine_box, rt_cumsum,
+ * rt_mask_compact, rt_axis_scan and rt_flat_copy (the contract of
+ * rt_take_rows): every argument is checked on the host before any HIP call
+ * and a bad one returns nonzero with rt_last_error() naming the entry point
+ * and the argument.  Rejected: nd out of range; NULL shape / strides; a
+ * negative extent; an extent of 2^40 or more or an extent product above
+ * 2^46 (the rt_arg_* limits); a dtype / elemsize / op / phase / scatter
+ * code outside the listed values; a NULL data pointer when there is work to
+ * do.  A zero extent returns 0 without launching.  Offsets and strides are
+ * NOT checked against the allocations (the entry points do not know their
+ * sizes): keeping the box inside both buffers is the caller's job. */
+
 /* Strided box copy between device buffers (pack/unpack/halo/gather).
- * shape/strides are in elements, nd <= 4, elemsize in {1,2,4,8}. */
+ * shape/strides are in elements, 1 <= nd <= 4, elemsize in {1,2,4,8}.
+ * One thread per element, at most 2048 blocks of 256 (grid-stride). */
 int rt_copy_box(uintptr_t stream, void *dst, const void *src, int nd,
                 const int64_t *shape, const int64_t *dst_strides,
                 const int64_t *src_strides, int64_t dst_off, int64_t src_off,
@@ -71,17 +84,28 @@ int rt_copy_box(uintptr_t stream, void *dst, const void *src, int nd,
 
 /* Typed combining box copy: dst = dst OP src (axis-reduction merge).
  * dtype: 0=f64 1=f32 2=i64 3=i32 4=i16 5=i8 6=u8;
- * op: 0=add 1=mul 2=min 3=max 4=logical_and 5=logical_or. */
+ * op: 0=add 1=mul 2=min 3=max 4=logical_and 5=logical_or.  Float min/max
+ * propagate NaN from either side; the logical ops write 0 or 1. */
 int rt_combine_box(uintptr_t stream, void *dst, const void *src, int nd,
                    const int64_t *shape, const int64_t *dst_strides,
                    const int64_t *src_strides, int64_t dst_off,
                    int64_t src_off, int dtype, int op);
 
+/* Elements per chunk of the rt_cumsum phases (one bsums slot each) and of
+ * rt_mask_compact (one bcounts slot each).  Host arithmetic only. */
+int rt_scan_chunk(void);
+int rt_mask_chunk(void);
+
 /* cumsum phases (local scan; cross-rank offset fixed up by the host):
- * phase 1: block sums into `bsums[nblocks]`; phase 2: one-block exclusive
- * scan of bsums in place + grand total into `total`; phase 3: apply with
- * `fbase`/`ibase` (the rank's global offset).  dtype: 0=f64 1=f32 2=i64
- * 3=i32. */
+ * phase 1: chunk sums into `bsums[ceil(n / rt_scan_chunk())]`; phase 2:
+ * one-block exclusive scan of bsums[0, nblocks) in place + grand total into
+ * `total` (may be NULL); phase 3: apply with `fbase`/`ibase` (the rank's
+ * global offset).  In phases 1 and 3 `nblocks` is the launch grid: the
+ * blocks stride over the chunks of n, so any value >= 1 is valid.
+ * dtype: 0=f64 1=f32 2=i64 3=i32; phase: 1, 2 or 3, anything else is
+ * rejected.  Needed pointers: in + bsums (1), bsums (2), in + out + bsums
+ * (3).  n == 0 returns 0 without launching in phases 1 and 3; phase 2
+ * ignores in / n / out. */
 int rt_cumsum(uintptr_t stream, const void *in, int64_t in_off,
               int64_t in_stride, int64_t n, void *out, int64_t out_off,
               void *bsums, int64_t nblocks, void *total, double fbase,
@@ -99,19 +123,42 @@ int rt_cumsum_scan(uintptr_t stream, const void *in, int64_t in_off,
 
 /* Ordered boolean-mask compaction over the rank's local core box, C
  * iteration order (reference: the compressing boolean getitem of
- * ramba.ndarray, ramba/ramba.py maskarray path).  phase 1: per-4096-chunk
- * selected counts into bcounts (int64[nchunks]); phase 2 is
- * rt_cumsum(phase=2, dtype=2) on bcounts (exclusive scan + total);
- * phase 3: write selected elements of `a` densely into `out`.
- * dtype: 0=f64 1=f32 2=i64 3=i32 4=i16 5=i8 6=u8. */
+ * ramba.ndarray, ramba/ramba.py maskarray path).  phase 1: selected counts
+ * per chunk of rt_mask_chunk() (2048) elements into bcounts
+ * (int64[nchunks]); phase 2 is rt_cumsum(phase=2, dtype=2) on bcounts
+ * (exclusive scan + total); phase 3: write selected elements of `a` densely
+ * into `out`.  nchunks must equal ceil(n / rt_mask_chunk()), n the extent
+ * product.  The mask is one byte per element, nonzero = selected; its
+ * counts are read 8 bytes at a time when it is 1-D, stride 1 and 8-byte
+ * aligned.  dtype: 0=f64 1=f32 2=i64 3=i32 4=i16 5=i8 6=u8; phase 1 or 3.
+ * Needed pointers: m + bcounts (1); a + m + out + bcounts (3). */
 int rt_mask_compact(uintptr_t stream, const void *a, const void *m,
                     void *out, int nd, const int64_t *shape,
                     const int64_t *a_strides, const int64_t *m_strides,
                     void *bcounts, int64_t nchunks, int dtype, int phase);
 
+/* Inclusive cumulative sum along `axis` of a strided box (the N-D half of
+ * the reference's scumulative, ramba/ramba.py:10057-10171).  in / out are
+ * pre-offset to the box origin; shape and both stride lists cover the full
+ * box, 2 <= nd <= 4, strides in elements.  totals: dense C-order array over
+ * the box with `axis` removed; receives each line's sum (its last scanned
+ * element).  dtype: 0=f64 1=f32 2=i64 3=i32.
+ * nchunks == 1: one wave per line when axis == nd-1, else one thread per
+ * line.  nchunks > 1: the axis is cut into nchunks ranges of
+ * ceil(len / nchunks), one thread per (line, range), with tot2
+ * (nchunks * nlines elements of the dtype) as scratch; trailing ranges may
+ * be empty.  nchunks < 1, or nchunks > 1 with tot2 == NULL, is rejected. */
+int rt_axis_scan(uintptr_t stream, const void *in, void *out, void *totals,
+                 int nd, const int64_t *shape, const int64_t *in_strides,
+                 const int64_t *out_strides, int axis, int dtype, void *tot2,
+                 int64_t nchunks);
+
 /* Flat C-order gather (scatter=0) / scatter (scatter=1) between a strided
  * local box and a dense buffer — the data movement of reshape (reference
- * flat-index remap worker, ramba/ramba.py:2409-2492). */
+ * flat-index remap worker, ramba/ramba.py:2409-2492).  `boxed` is
+ * pre-offset to the box origin; [flat0, flat0 + n) is a C-order flat
+ * subrange of the box and must lie inside it (flat0 >= 0, n >= 0,
+ * flat0 + n <= extent product).  elemsize in {1,2,4,8}. */
 int rt_flat_copy(uintptr_t stream, void *boxed, void *dense, int nd,
                  const int64_t *shape, const int64_t *strides,
                  int64_t flat0, int64_t n, int elemsize, int scatter);

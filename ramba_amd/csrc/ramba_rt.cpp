@@ -40,6 +40,39 @@ void set_error(const std::string &msg) {
         }                                                                  \
     } while (0)
 
+int fail(const char *who, const char *what) {
+    set_error(std::string(who) + ": " + what);
+    return 1;
+}
+
+// Host-side geometry check shared by the box-shaped entry points
+// (rt_copy_box, rt_combine_box, rt_mask_compact, rt_axis_scan,
+// rt_flat_copy); runs before any HIP call.  Extents may be zero (the entry
+// then returns 0 without launching) but not negative; the size limits are
+// those of rt_arg_* (an extent under 2^40, a product of at most 2^46), so
+// no element count or flat index can overflow int64.  *n_out = product.
+int box_extents(const char *who, int nd, int nd_min, const int64_t *shape,
+                const int64_t *str_a, const int64_t *str_b, int64_t *n_out) {
+    if (nd < nd_min || nd > 4) return fail(who, "nd out of range");
+    if (!shape) return fail(who, "NULL shape");
+    if (!str_a || !str_b) return fail(who, "NULL strides");
+    int64_t n = 1;
+    bool empty = false;
+    for (int d = 0; d < nd; ++d) {
+        if (shape[d] < 0) return fail(who, "negative extent in shape");
+        if (shape[d] >= (1LL << 40))
+            return fail(who, "extent in shape out of range");
+        if (shape[d] == 0) empty = true;
+    }
+    for (int d = 0; d < nd && !empty; ++d) {
+        if (n > (1LL << 46) / shape[d])
+            return fail(who, "shape too large (extent product overflows)");
+        n *= shape[d];
+    }
+    *n_out = empty ? 0 : n;
+    return 0;
+}
+
 struct Kernel {
     hipModule_t module = nullptr;
     hipFunction_t func = nullptr;
@@ -359,25 +392,25 @@ extern "C" int rt_combine_box(uintptr_t stream, void *dst, const void *src,
                               const int64_t *dst_strides,
                               const int64_t *src_strides, int64_t dst_off,
                               int64_t src_off, int dtype, int op) {
-    if (nd < 1 || nd > 4) {
-        set_error("rt_combine_box: nd out of range");
-        return 1;
-    }
     BoxArgs a;
+    if (box_extents("rt_combine_box", nd, 1, shape, dst_strides, src_strides,
+                    &a.n))
+        return 1;
+    if (dtype < 0 || dtype > 6) return fail("rt_combine_box", "bad dtype");
+    if (op < 0 || op > 5) return fail("rt_combine_box", "bad op");
+    if (a.n == 0) return 0;
+    if (!dst || !src) return fail("rt_combine_box", "NULL dst/src");
     a.nd = nd;
-    a.n = 1;
     for (int d = 0; d < nd; ++d) {
         a.shape[d] = shape[d];
         a.dstr[d] = dst_strides[d];
         a.sstr[d] = src_strides[d];
-        a.n *= shape[d];
     }
     for (int d = nd; d < 4; ++d) {
         a.shape[d] = 1;
         a.dstr[d] = 0;
         a.sstr[d] = 0;
     }
-    if (a.n == 0) return 0;
     switch (dtype) {
         case 0: return box_combine_launch<double>(
             stream, static_cast<char *>(dst) + dst_off * 8,
@@ -411,25 +444,25 @@ extern "C" int rt_copy_box(uintptr_t stream, void *dst, const void *src,
                            const int64_t *dst_strides,
                            const int64_t *src_strides, int64_t dst_off,
                            int64_t src_off, int elemsize) {
-    if (nd < 1 || nd > 4) {
-        set_error("rt_copy_box: nd out of range");
-        return 1;
-    }
     BoxArgs a;
+    if (box_extents("rt_copy_box", nd, 1, shape, dst_strides, src_strides,
+                    &a.n))
+        return 1;
+    if (elemsize != 1 && elemsize != 2 && elemsize != 4 && elemsize != 8)
+        return fail("rt_copy_box", "bad elemsize");
+    if (a.n == 0) return 0;
+    if (!dst || !src) return fail("rt_copy_box", "NULL dst/src");
     a.nd = nd;
-    a.n = 1;
     for (int d = 0; d < nd; ++d) {
         a.shape[d] = shape[d];
         a.dstr[d] = dst_strides[d];
         a.sstr[d] = src_strides[d];
-        a.n *= shape[d];
     }
     for (int d = nd; d < 4; ++d) {
         a.shape[d] = 1;
         a.dstr[d] = 0;
         a.sstr[d] = 0;
     }
-    if (a.n == 0) return 0;
     char *d8 = static_cast<char *>(dst) + dst_off * elemsize;
     const char *s8 = static_cast<const char *>(src) + src_off * elemsize;
     switch (elemsize) {
@@ -783,13 +816,15 @@ int cumsum_launch(uintptr_t stream, const void *in, int64_t in_off,
         hipLaunchKernelGGL((cumsum_k2<T>), dim3(1), dim3(SCAN_THREADS), 0, st,
                            static_cast<T *>(bsums), nblocks,
                            static_cast<T *>(total));
-    } else {
+    } else if (phase == 3) {
         T base = (T)fbase;
         if (sizeof(T) >= 4 && (T)0.5 == 0) base = (T)ibase;  // integer T
         hipLaunchKernelGGL((cumsum_k3<T>), dim3(grid), dim3(SCAN_THREADS), 0,
                            st, static_cast<const T *>(in), in_off, in_stride,
                            n, static_cast<T *>(out), out_off,
                            static_cast<const T *>(bsums), base);
+    } else {
+        return fail("rt_cumsum", "bad phase");
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
@@ -834,6 +869,17 @@ extern "C" int rt_cumsum(uintptr_t stream, const void *in, int64_t in_off,
                          int64_t out_off, void *bsums, int64_t nblocks,
                          void *total, double fbase, int64_t ibase,
                          int dtype, int phase) {
+    if (dtype < 0 || dtype > 3) return fail("rt_cumsum", "bad dtype");
+    if (phase < 1 || phase > 3) return fail("rt_cumsum", "bad phase");
+    if (n < 0) return fail("rt_cumsum", "negative n");
+    // phases 1 and 3 use nblocks as their grid (the kernels stride over the
+    // chunks of n); phase 2 scans bsums[0, nblocks) in one block
+    if (nblocks < 1) return fail("rt_cumsum", "nblocks < 1");
+    if (nblocks >= (1LL << 31)) return fail("rt_cumsum", "nblocks too large");
+    if (phase != 2 && n == 0) return 0;
+    if (!bsums) return fail("rt_cumsum", "NULL bsums");
+    if (phase != 2 && !in) return fail("rt_cumsum", "NULL in");
+    if (phase == 3 && !out) return fail("rt_cumsum", "NULL out");
     switch (dtype) {
         case 0: return cumsum_launch<double>(stream, in, in_off, in_stride, n,
                                              out, out_off, bsums, nblocks,
@@ -1038,36 +1084,48 @@ int mask_compact_launch(uintptr_t stream, const void *a, const void *m,
 
 }  // namespace
 
+// chunk sizes the host sizes bsums / bcounts by
+extern "C" int rt_scan_chunk(void) { return SCAN_CHUNK; }
+extern "C" int rt_mask_chunk(void) { return MC_CHUNK; }
+
 // phase 1: bcounts[c] = selected count of chunk c (nchunks =
-// ceil(n/4096) int64 slots).  Phase 2 is rt_cumsum(phase=2, dtype=2) on
-// bcounts.  Phase 3: ordered write into dense `out`.  a/m pointers are
-// pre-offset by the caller; strides/shape describe the local box.
-// dtype: 0=f64 1=f32 2=i64 3=i32 4=i16 5=i8 6=u8.
+// ceil(n / rt_mask_chunk()) int64 slots, 2048-element chunks).  Phase 2 is
+// rt_cumsum(phase=2, dtype=2) on bcounts.  Phase 3: ordered write into
+// dense `out`.  a/m pointers are pre-offset by the caller; strides/shape
+// describe the local box.  dtype: 0=f64 1=f32 2=i64 3=i32 4=i16 5=i8 6=u8.
 extern "C" int rt_mask_compact(uintptr_t stream, const void *a,
                                const void *m, void *out, int nd,
                                const int64_t *shape,
                                const int64_t *a_strides,
                                const int64_t *m_strides, void *bcounts,
                                int64_t nchunks, int dtype, int phase) {
-    if (nd < 1 || nd > 4) {
-        set_error("rt_mask_compact: nd out of range");
-        return 1;
-    }
     MCArgs g;
+    if (box_extents("rt_mask_compact", nd, 1, shape, a_strides, m_strides,
+                    &g.n))
+        return 1;
+    if (dtype < 0 || dtype > 6) return fail("rt_mask_compact", "bad dtype");
+    if (phase != 1 && phase != 3)
+        return fail("rt_mask_compact", "bad phase (1 or 3; phase 2 is "
+                                       "rt_cumsum)");
+    if (g.n == 0) return 0;
+    // every chunk of n writes (phase 1) or reads (phase 3) its bcounts slot
+    if (nchunks != (g.n + MC_CHUNK - 1) / MC_CHUNK)
+        return fail("rt_mask_compact", "nchunks is not ceil(n / chunk)");
+    if (!m) return fail("rt_mask_compact", "NULL m");
+    if (!bcounts) return fail("rt_mask_compact", "NULL bcounts");
+    if (phase == 3 && (!a || !out))
+        return fail("rt_mask_compact", "NULL a/out");
     g.nd = nd;
-    g.n = 1;
     for (int d = 0; d < nd; ++d) {
         g.shape[d] = shape[d];
         g.astr[d] = a_strides[d];
         g.mstr[d] = m_strides[d];
-        g.n *= shape[d];
     }
     for (int d = nd; d < 4; ++d) {
         g.shape[d] = 1;
         g.astr[d] = 0;
         g.mstr[d] = 0;
     }
-    if (g.n == 0) return 0;
     switch (dtype) {
         case 0: return mask_compact_launch<double>(stream, a, m, out, g,
                                                    bcounts, nchunks, phase);
@@ -1309,10 +1367,19 @@ extern "C" int rt_axis_scan(uintptr_t stream, const void *in, void *out,
                             const int64_t *in_strides,
                             const int64_t *out_strides, int axis,
                             int dtype, void *tot2, int64_t nchunks) {
-    if (nd < 2 || nd > 4 || axis < 0 || axis >= nd) {
-        set_error("rt_axis_scan: bad nd/axis");
+    int64_t nbox = 0;
+    if (box_extents("rt_axis_scan", nd, 2, shape, in_strides, out_strides,
+                    &nbox))
         return 1;
-    }
+    if (axis < 0 || axis >= nd)
+        return fail("rt_axis_scan", "axis out of range");
+    if (dtype < 0 || dtype > 3) return fail("rt_axis_scan", "bad dtype");
+    if (nchunks < 1) return fail("rt_axis_scan", "nchunks < 1");
+    if (nchunks > 1 && !tot2)
+        return fail("rt_axis_scan", "nchunks > 1 needs tot2");
+    if (nbox == 0) return 0;
+    if (!in || !out || !totals)
+        return fail("rt_axis_scan", "NULL in/out/totals");
     ASArgs g;
     g.len = shape[axis];
     g.istr_ax = in_strides[axis];
@@ -1332,8 +1399,9 @@ extern "C" int rt_axis_scan(uintptr_t stream, const void *in, void *out,
         g.istr[d] = 0;
         g.ostr[d] = 0;
     }
-    if (g.nlines == 0 || g.len == 0) return 0;
-    if (nchunks > 1 && tot2) {
+    if (nchunks > (1LL << 46) / g.nlines)
+        return fail("rt_axis_scan", "nchunks * lines too large");
+    if (nchunks > 1) {
         switch (dtype) {
             case 0: return axis_scan_chunked_launch<double>(
                 stream, in, out, totals, tot2, g, nchunks);
@@ -1496,10 +1564,19 @@ extern "C" int rt_flat_copy(uintptr_t stream, void *boxed, void *dense,
                             int nd, const int64_t *shape,
                             const int64_t *strides, int64_t flat0,
                             int64_t n, int elemsize, int scatter) {
-    if (nd < 1 || nd > 4) {
-        set_error("rt_flat_copy: nd out of range");
+    int64_t nbox = 0;
+    if (box_extents("rt_flat_copy", nd, 1, shape, strides, strides, &nbox))
         return 1;
-    }
+    if (elemsize != 1 && elemsize != 2 && elemsize != 4 && elemsize != 8)
+        return fail("rt_flat_copy", "bad elemsize");
+    if (scatter != 0 && scatter != 1)
+        return fail("rt_flat_copy", "bad scatter (0 or 1)");
+    if (flat0 < 0) return fail("rt_flat_copy", "negative flat0");
+    if (n < 0) return fail("rt_flat_copy", "negative n");
+    if (flat0 > nbox || n > nbox - flat0)
+        return fail("rt_flat_copy", "flat0 + n past the end of the box");
+    if (n == 0) return 0;
+    if (!boxed || !dense) return fail("rt_flat_copy", "NULL boxed/dense");
     FlatArgs g;
     g.nd = nd;
     g.n = n;

@@ -106,6 +106,8 @@ def _load_lib():
                                    ctypes.c_int]
     _vp, _i64, _int = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
     lib.rt_arg_grid_cap.restype = ctypes.c_int
+    lib.rt_scan_chunk.restype = ctypes.c_int
+    lib.rt_mask_chunk.restype = ctypes.c_int
     lib.rt_arg_flat_regime.argtypes = [_vp, _i64, _int, _p64, _p64, _int]
     lib.rt_arg_flat.argtypes = [ctypes.c_size_t, _vp, _i64, _int, _p64,
                                 _p64, _p64, _i64, _int, _int, _int, _vp,
@@ -647,7 +649,6 @@ HipBackend.combine_temp_into_container = _hb_combine_temp_into_container
 # -- cumsum --------------------------------------------------
 
 _CS_DT = {"float64": 0, "float32": 1, "int64": 2, "int32": 3}
-_SCAN_CHUNK = 4096
 
 
 def _hb_cumsum_src(self, bd, off0, stride, n, out_dtype):
@@ -679,7 +680,8 @@ def _hb_cumsum_local_phase12(self, bd, off0, stride, n, out_dtype):
         # guide §price list).  Default stays 3-phase.
         self.temps["__cs_state__"] = (src, off0, stride, n, 0, dt)
         return np.asarray(0, dtype=out_dtype)[()]
-    nblocks = max(1, (n + _SCAN_CHUNK - 1) // _SCAN_CHUNK)
+    chunk = self.lib.rt_scan_chunk()
+    nblocks = max(1, (n + chunk - 1) // chunk)
     bsums = self.torch.empty(nblocks, dtype=self._tdt(out_dtype),
                              device="cuda")
     total = self.torch.empty(1, dtype=self._tdt(out_dtype), device="cuda")
@@ -773,8 +775,8 @@ def _hb_mask_compact(self, bd_a, bd_m, rt):
     a_ptr = ca.data_ptr() + off_a * ca.element_size()
     m_ptr = cm.data_ptr() + off_m * cm.element_size()
     dtc = _MC_DT[str(np.dtype(bd_a.dtype))]
-    _MC_CHUNK = 2048     # must match MC_CHUNK in ramba_rt.cpp
-    nchunks = max(1, (n + _MC_CHUNK - 1) // _MC_CHUNK)
+    chunk = self.lib.rt_mask_chunk()
+    nchunks = max(1, (n + chunk - 1) // chunk)
     bcounts = self.torch.empty(nchunks, dtype=self.torch.int64,
                                device="cuda")
     total = self.torch.empty(1, dtype=self.torch.int64, device="cuda")
