@@ -23,8 +23,8 @@
  *   rt_device_sync    — worker-side completion (sync, ramba.py:9843)
  *   rt_event_*        — hot-loop timing (add_time, ramba.py:945-1022)
  *
- * Python-side binding a maintainer would write: see INTEGRATION.md
- * (ctypes stub).
+ * Python-side binding: the ctypes table in ramba_amd/hip_backend.py
+ * (_load_lib); see INTEGRATION.md.
  */
 
 #ifndef RAMBA_RT_H
@@ -41,6 +41,16 @@ extern "C" {
  * returns a static string describing the last failure (fail-fast contract —
  * the analog of the reference's ("ERROR", worker, traceback) reply,
  * ramba.py:3878-3881). */
+
+/* Element-type codes of every `int dtype` parameter below.  This is the one
+ * statement of the list: the runtime dispatches on these names and the
+ * Python binding's RT_DTYPE table mirrors them.
+ *   RT_F64 double   RT_F32 float    RT_I64 int64_t   RT_I32 int32_t
+ *   RT_I16 int16_t  RT_I8  int8_t   RT_U8  uint8_t (also bool)
+ * rt_cumsum and rt_axis_scan take the first four (RT_F64 .. RT_I32);
+ * rt_combine_box, rt_mask_compact and the rt_arg_* family take all seven.
+ * Any other value is rejected with "<entry>: bad dtype". */
+enum rt_dtype { RT_F64 = 0, RT_F32, RT_I64, RT_I32, RT_I16, RT_I8, RT_U8 };
 
 int         rt_init(int device);
 int         rt_device_count(void);
@@ -83,7 +93,7 @@ int rt_copy_box(uintptr_t stream, void *dst, const void *src, int nd,
                 int elemsize);
 
 /* Typed combining box copy: dst = dst OP src (axis-reduction merge).
- * dtype: 0=f64 1=f32 2=i64 3=i32 4=i16 5=i8 6=u8;
+ * dtype: any rt_dtype;
  * op: 0=add 1=mul 2=min 3=max 4=logical_and 5=logical_or.  Float min/max
  * propagate NaN from either side; the logical ops write 0 or 1. */
 int rt_combine_box(uintptr_t stream, void *dst, const void *src, int nd,
@@ -102,7 +112,7 @@ int rt_mask_chunk(void);
  * `total` (may be NULL); phase 3: apply with `fbase`/`ibase` (the rank's
  * global offset).  In phases 1 and 3 `nblocks` is the launch grid: the
  * blocks stride over the chunks of n, so any value >= 1 is valid.
- * dtype: 0=f64 1=f32 2=i64 3=i32; phase: 1, 2 or 3, anything else is
+ * dtype: RT_F64 .. RT_I32; phase: 1, 2 or 3, anything else is
  * rejected.  Needed pointers: in + bsums (1), bsums (2), in + out + bsums
  * (3).  n == 0 returns 0 without launching in phases 1 and 3; phase 2
  * ignores in / n / out. */
@@ -111,26 +121,16 @@ int rt_cumsum(uintptr_t stream, const void *in, int64_t in_off,
               void *bsums, int64_t nblocks, void *total, double fbase,
               int64_t ibase, int dtype, int phase);
 
-/* single-pass decoupled-lookback cumsum (one read + one write per
- * element; the chained cross-workgroup hand-off follows the CDNA4
- * guide's agent-atomic discipline).  agg/inc: u64[nchunks]; flag:
- * u32[nchunks] and ticket: u32[1], both zeroed by the host before every
- * launch. */
-int rt_cumsum_scan(uintptr_t stream, const void *in, int64_t in_off,
-                   int64_t in_stride, int64_t n, void *out, int64_t out_off,
-                   void *agg, void *inc, void *flag, void *ticket,
-                   double fbase, int64_t ibase, int dtype);
-
 /* Ordered boolean-mask compaction over the rank's local core box, C
  * iteration order (reference: the compressing boolean getitem of
  * ramba.ndarray, ramba/ramba.py maskarray path).  phase 1: selected counts
  * per chunk of rt_mask_chunk() (2048) elements into bcounts
- * (int64[nchunks]); phase 2 is rt_cumsum(phase=2, dtype=2) on bcounts
+ * (int64[nchunks]); phase 2 is rt_cumsum(phase=2, dtype=RT_I64) on bcounts
  * (exclusive scan + total); phase 3: write selected elements of `a` densely
  * into `out`.  nchunks must equal ceil(n / rt_mask_chunk()), n the extent
  * product.  The mask is one byte per element, nonzero = selected; its
  * counts are read 8 bytes at a time when it is 1-D, stride 1 and 8-byte
- * aligned.  dtype: 0=f64 1=f32 2=i64 3=i32 4=i16 5=i8 6=u8; phase 1 or 3.
+ * aligned.  dtype: any rt_dtype; phase 1 or 3.
  * Needed pointers: m + bcounts (1); a + m + out + bcounts (3). */
 int rt_mask_compact(uintptr_t stream, const void *a, const void *m,
                     void *out, int nd, const int64_t *shape,
@@ -142,7 +142,7 @@ int rt_mask_compact(uintptr_t stream, const void *a, const void *m,
  * pre-offset to the box origin; shape and both stride lists cover the full
  * box, 2 <= nd <= 4, strides in elements.  totals: dense C-order array over
  * the box with `axis` removed; receives each line's sum (its last scanned
- * element).  dtype: 0=f64 1=f32 2=i64 3=i32.
+ * element).  dtype: RT_F64 .. RT_I32.
  * nchunks == 1: one wave per line when axis == nd-1, else one thread per
  * line.  nchunks > 1: the axis is cut into nchunks ranges of
  * ceil(len / nchunks), one thread per (line, range), with tot2
@@ -194,7 +194,7 @@ int rt_take_regime(const void *dst, const void *src, int nd_inner,
  * (the reference lists them as to-do, ramba/ramba.py:10288).  One pass over
  * a strided box of 1..4 axes at `in + in_off` (offset and strides in
  * elements); every merge uses rt_arg_better (include/ramba_argcmp.h).
- * dtype: 0=f64 1=f32 2=i64 3=i32 4=i16 5=i8 6=u8 (bool).  Reported indices
+ * dtype: any rt_dtype (bool is RT_U8).  Reported indices
  * are idx0 + sum_d coord_d * mult_d; -1 = no candidate (skipna, all NaN).
  * mult must make the index grow with C order over the box (the C strides
  * of an enclosing shape, or 1 on the reduced axis): threads rely on it.

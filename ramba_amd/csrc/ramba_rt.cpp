@@ -73,6 +73,60 @@ int box_extents(const char *who, int nd, int nd_min, const int64_t *shape,
     return 0;
 }
 
+// Status of the kernel launch(es) just issued; a failure is reported as
+// "<what> launch: <hip error>".
+int launched(const char *what) {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        set_error(std::string(what) + " launch: " + hipGetErrorString(e));
+        return 1;
+    }
+    return 0;
+}
+
+// The one rt_dtype -> element type mapping: runs call(T()) for the type of
+// `dtype`.  NCODES is how many codes the entry point accepts, 4 (RT_F64 ..
+// RT_I32) or 7 (all); the types of the other codes are never instantiated.
+// Entry points range-check dtype with their other arguments, so the last
+// line is not reached from them.
+template <int NCODES, typename F>
+int dtype_dispatch(const char *who, int dtype, F call) {
+    static_assert(NCODES == 4 || NCODES == 7, "4 or 7 dtype codes");
+    switch (dtype) {
+        case RT_F64: return call(double());
+        case RT_F32: return call(float());
+        case RT_I64: return call(int64_t());
+        case RT_I32: return call(int32_t());
+    }
+    if constexpr (NCODES == 7) {
+        switch (dtype) {
+            case RT_I16: return call(int16_t());
+            case RT_I8: return call(int8_t());
+            case RT_U8: return call(uint8_t());
+        }
+    }
+    return fail(who, "bad dtype");
+}
+
+// element size of a (range-checked) rt_dtype code
+int dtype_size(int dtype) {
+    return dtype_dispatch<7>("dtype_size", dtype,
+                             [](auto t) { return (int)sizeof(t); });
+}
+
+// Kernel geometry: copy nd extents and one or two stride lists into the
+// 4-slot arrays of an argument struct, padding the unused axes with extent
+// 1, stride 0.
+void fill_geom(int nd, const int64_t *shape, int64_t *gshape,
+               const int64_t *str_a, int64_t *gstr_a,
+               const int64_t *str_b = nullptr, int64_t *gstr_b = nullptr) {
+    for (int d = 0; d < 4; ++d) {
+        gshape[d] = d < nd ? shape[d] : 1;
+        gstr_a[d] = d < nd ? str_a[d] : 0;
+        if (gstr_b) gstr_b[d] = d < nd ? str_b[d] : 0;
+    }
+}
+
 struct Kernel {
     hipModule_t module = nullptr;
     hipFunction_t func = nullptr;
@@ -310,12 +364,7 @@ int box_copy_launch(uintptr_t stream, void *dst, const void *src,
     hipLaunchKernelGGL(box_copy_kernel<T>, dim3((unsigned)blocks), dim3(256),
                        0, reinterpret_cast<hipStream_t>(stream),
                        static_cast<T *>(dst), static_cast<const T *>(src), a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error(std::string("box_copy launch: ") + hipGetErrorString(e));
-        return 1;
-    }
-    return 0;
+    return launched("box_copy");
 }
 
 }  // namespace
@@ -375,18 +424,13 @@ int box_combine_launch(uintptr_t stream, void *dst, const void *src,
             set_error("rt_combine_box: bad op");
             return 1;
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error(std::string("box_combine launch: ") + hipGetErrorString(e));
-        return 1;
-    }
-    return 0;
+    return launched("box_combine");
 }
 
 }  // namespace
 
-// dtype: 0=f64 1=f32 2=i64 3=i32 4=i16 5=i8 6=u8; op: 0=add 1=mul 2=min
-// 3=max 4=logical_and 5=logical_or
+// dtype: any rt_dtype; op: 0=add 1=mul 2=min 3=max 4=logical_and
+// 5=logical_or
 extern "C" int rt_combine_box(uintptr_t stream, void *dst, const void *src,
                               int nd, const int64_t *shape,
                               const int64_t *dst_strides,
@@ -396,47 +440,19 @@ extern "C" int rt_combine_box(uintptr_t stream, void *dst, const void *src,
     if (box_extents("rt_combine_box", nd, 1, shape, dst_strides, src_strides,
                     &a.n))
         return 1;
-    if (dtype < 0 || dtype > 6) return fail("rt_combine_box", "bad dtype");
+    if (dtype < RT_F64 || dtype > RT_U8)
+        return fail("rt_combine_box", "bad dtype");
     if (op < 0 || op > 5) return fail("rt_combine_box", "bad op");
     if (a.n == 0) return 0;
     if (!dst || !src) return fail("rt_combine_box", "NULL dst/src");
     a.nd = nd;
-    for (int d = 0; d < nd; ++d) {
-        a.shape[d] = shape[d];
-        a.dstr[d] = dst_strides[d];
-        a.sstr[d] = src_strides[d];
-    }
-    for (int d = nd; d < 4; ++d) {
-        a.shape[d] = 1;
-        a.dstr[d] = 0;
-        a.sstr[d] = 0;
-    }
-    switch (dtype) {
-        case 0: return box_combine_launch<double>(
-            stream, static_cast<char *>(dst) + dst_off * 8,
-            static_cast<const char *>(src) + src_off * 8, a, op);
-        case 1: return box_combine_launch<float>(
-            stream, static_cast<char *>(dst) + dst_off * 4,
-            static_cast<const char *>(src) + src_off * 4, a, op);
-        case 2: return box_combine_launch<int64_t>(
-            stream, static_cast<char *>(dst) + dst_off * 8,
-            static_cast<const char *>(src) + src_off * 8, a, op);
-        case 3: return box_combine_launch<int32_t>(
-            stream, static_cast<char *>(dst) + dst_off * 4,
-            static_cast<const char *>(src) + src_off * 4, a, op);
-        case 4: return box_combine_launch<int16_t>(
-            stream, static_cast<char *>(dst) + dst_off * 2,
-            static_cast<const char *>(src) + src_off * 2, a, op);
-        case 5: return box_combine_launch<int8_t>(
-            stream, static_cast<char *>(dst) + dst_off,
-            static_cast<const char *>(src) + src_off, a, op);
-        case 6: return box_combine_launch<uint8_t>(
-            stream, static_cast<char *>(dst) + dst_off,
-            static_cast<const char *>(src) + src_off, a, op);
-        default:
-            set_error("rt_combine_box: bad dtype");
-            return 1;
-    }
+    fill_geom(nd, shape, a.shape, dst_strides, a.dstr, src_strides, a.sstr);
+    return dtype_dispatch<7>("rt_combine_box", dtype, [&](auto t) {
+        using T = decltype(t);
+        return box_combine_launch<T>(stream, static_cast<T *>(dst) + dst_off,
+                                     static_cast<const T *>(src) + src_off,
+                                     a, op);
+    });
 }
 
 extern "C" int rt_copy_box(uintptr_t stream, void *dst, const void *src,
@@ -453,16 +469,7 @@ extern "C" int rt_copy_box(uintptr_t stream, void *dst, const void *src,
     if (a.n == 0) return 0;
     if (!dst || !src) return fail("rt_copy_box", "NULL dst/src");
     a.nd = nd;
-    for (int d = 0; d < nd; ++d) {
-        a.shape[d] = shape[d];
-        a.dstr[d] = dst_strides[d];
-        a.sstr[d] = src_strides[d];
-    }
-    for (int d = nd; d < 4; ++d) {
-        a.shape[d] = 1;
-        a.dstr[d] = 0;
-        a.sstr[d] = 0;
-    }
+    fill_geom(nd, shape, a.shape, dst_strides, a.dstr, src_strides, a.sstr);
     char *d8 = static_cast<char *>(dst) + dst_off * elemsize;
     const char *s8 = static_cast<const char *>(src) + src_off * elemsize;
     switch (elemsize) {
@@ -488,6 +495,11 @@ namespace {
 constexpr int SCAN_THREADS = 256;
 constexpr int SCAN_ITEMS = 16;
 constexpr int SCAN_CHUNK = SCAN_THREADS * SCAN_ITEMS;
+
+// LDS index of chunk element g in the staged kernels (cumsum_k3,
+// mask_write_k): one pad element per 16 keeps a thread's contiguous reads
+// off a 32-way bank conflict
+#define LIDX(g) ((g) + ((g) >> 4))
 
 template <typename T>
 __global__ __launch_bounds__(256) void cumsum_k1(const T *__restrict__ in,
@@ -565,9 +577,8 @@ __global__ __launch_bounds__(256) void cumsum_k3(const T *__restrict__ in,
     // stage the chunk through LDS so global loads AND stores stay
     // coalesced (per-lane contiguous-16 global stores are partial-line
     // read-modify-write: measured 572 GB/s -> LDS-staged ~streaming
-    // rate).  One pad element per 16 keeps the per-thread contiguous
+    // rate).  One pad element per 16 (LIDX) keeps the per-thread contiguous
     // reads off a 32-way bank conflict.  ~35 KB of LDS for fp64 chunks.
-#define LIDX(g) ((g) + ((g) >> 4))
     __shared__ T lds[SCAN_CHUNK + SCAN_THREADS];
     int64_t blk = blockIdx.x;
     int64_t nblocks = gridDim.x;
@@ -619,188 +630,6 @@ __global__ __launch_bounds__(256) void cumsum_k3(const T *__restrict__ in,
     }
 }
 
-// ---- single-pass decoupled-lookback scan -------------------------------
-// One read + one write per element (the 3-phase version re-reads the
-// input).  Chunks are claimed in order through a device ticket, so a
-// block only ever waits on chunks whose owners already started -- no
-// residency assumption (CDNA4 guide §6 G16: placement-independent).
-// All cross-workgroup words use 8-byte agent-scope atomics ("8-B agent
-// atomics both sides" valid form); the payload->flag order is still
-// protected by an asm vmcnt(0) drain (compiler-hazard workaround, G16
-// pitfall 12).  flag: 0 = empty, 1 = aggregate ready, 2 = inclusive
-// prefix ready.  The host zeroes ticket/flags before every launch
-// ("Re-initialise every call").
-
-#define GU64 __attribute__((address_space(1))) unsigned long long
-#define GU32 __attribute__((address_space(1))) unsigned int
-
-template <typename T>
-union BitsT {
-    T v;
-    unsigned long long b;
-};
-
-template <typename T>
-__device__ __forceinline__ void pub_u64(GU64 *p, T v) {
-    BitsT<T> u;
-    u.b = 0;
-    u.v = v;
-    __hip_atomic_store(p, u.b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-template <typename T>
-__device__ __forceinline__ T rd_u64(GU64 *p) {
-    BitsT<T> u;
-    u.b = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return u.v;
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void cumsum_lookback(
-    const T *__restrict__ in, int64_t in_off, int64_t in_stride, int64_t n,
-    T *__restrict__ out, int64_t out_off, GU64 *agg, GU64 *inc, GU32 *flag,
-    GU32 *ticket, T base) {
-    constexpr int ITEMS = 32;                 // 8192-elem chunks halve the
-    constexpr int CHUNK = 256 * ITEMS;        // cross-chunk chain length
-#define LIDX(g) ((g) + ((g) >> 4))
-    __shared__ T lds[CHUNK + CHUNK / 16];
-    __shared__ T wsum[4];
-    __shared__ unsigned long long tick_s;
-    __shared__ T excl_s;
-    const int64_t nchunks = (n + CHUNK - 1) / CHUNK;
-    for (;;) {
-        if (threadIdx.x == 0)
-            tick_s = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED,
-                                            __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        const int64_t t = (int64_t)tick_s;
-        if (t >= nchunks) return;
-        const int64_t b0 = t * (int64_t)CHUNK;
-        for (int j = 0; j < ITEMS; ++j) {
-            int64_t i = b0 + j * 256 + threadIdx.x;
-            if (i < n) lds[LIDX(j * 256 + threadIdx.x)] =
-                in[in_off + i * in_stride];
-        }
-        __syncthreads();
-        int64_t l0 = (int64_t)threadIdx.x * ITEMS;
-        int64_t lmax = n - b0;
-        T s = (T)0;
-        for (int j = 0; j < ITEMS; ++j)
-            if (l0 + j < lmax) s += lds[LIDX(l0 + j)];
-        T x = s;
-        int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-        for (int off = 1; off < 64; off <<= 1) {
-            T y = __shfl_up(x, off, 64);
-            if (lane >= off) x += y;
-        }
-        if (lane == 63) wsum[wid] = x;
-        __syncthreads();
-        T wbase = (T)0;
-        for (int w = 0; w < wid; ++w) wbase += wsum[w];
-        T below = __shfl_up(x, 1, 64);
-        T thread_excl = wbase + (lane > 0 ? below : (T)0);
-        T block_total = (T)0;
-        for (int w = 0; w < 4; ++w) block_total += wsum[w];
-        // publish aggregate; wave 0 then resolves the exclusive prefix by
-        // a WAVE-PARALLEL lookback: 64 predecessor states per hop
-        if (threadIdx.x == 0) {
-            pub_u64(agg + t, block_total);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __hip_atomic_store(flag + t, 1u, __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-        }
-        if (wid == 0) {
-            T running = (T)0;
-            int64_t p = t - 1;
-            unsigned spins = 0;
-            while (p >= 0) {
-                int64_t q = p - lane;
-                unsigned st = q >= 0
-                    ? __hip_atomic_load(flag + q, __ATOMIC_RELAXED,
-                                        __HIP_MEMORY_SCOPE_AGENT)
-                    : 2u;
-                unsigned long long incl = __ballot(st >= 2u);
-                unsigned long long zero = __ballot(st == 0u);
-                int k = incl ? __ffsll((unsigned long long)incl) - 1 : -1;
-                int zk = zero ? __ffsll((unsigned long long)zero) - 1 : 64;
-                if (k >= 0 && zk > k) {
-                    // complete prefix: aggregates for lanes < k, the
-                    // inclusive at lane k
-                    T v = (T)0;
-                    if (lane < k) v = rd_u64<T>(agg + q);
-                    else if (lane == k && q >= 0) v = rd_u64<T>(inc + q);
-                    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-                    running += __shfl(v, 0, 64);
-                    p = -1;
-                    break;
-                }
-                if (zk >= 64) {
-                    // 64 complete partials: take them all, keep walking
-                    T v = q >= 0 ? rd_u64<T>(agg + q) : (T)0;
-                    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-                    running += __shfl(v, 0, 64);
-                    p -= 64;
-                    continue;
-                }
-                ++spins;
-                if (spins > 4096) __builtin_amdgcn_s_sleep(32);
-                else __builtin_amdgcn_s_sleep(1);
-            }
-            if (lane == 0) {
-                T excl = base + running;
-                pub_u64(inc + t, excl + block_total);
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __hip_atomic_store(flag + t, 2u, __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-                excl_s = excl;
-            }
-        }
-        __syncthreads();
-        const T bbase = excl_s;
-        T run = bbase + thread_excl;
-        for (int j = 0; j < ITEMS; ++j) {
-            if (l0 + j < lmax) {
-                run += lds[LIDX(l0 + j)];
-                lds[LIDX(l0 + j)] = run;
-            }
-        }
-        __syncthreads();
-        for (int j = 0; j < ITEMS; ++j) {
-            int64_t i = b0 + j * 256 + threadIdx.x;
-            if (i < n) out[out_off + i] =
-                lds[LIDX(j * 256 + threadIdx.x)];
-        }
-        __syncthreads();
-    }
-#undef LIDX
-}
-
-template <typename T>
-int cumsum_lookback_launch(uintptr_t stream, const void *in, int64_t in_off,
-                           int64_t in_stride, int64_t n, void *out,
-                           int64_t out_off, void *agg, void *inc, void *flag,
-                           void *ticket, double fbase, int64_t ibase) {
-    T base = (T)fbase;
-    if ((T)0.5 == 0) base = (T)ibase;  // integer T
-    int64_t nchunks = (n + 8191) / 8192;
-    int64_t grid = nchunks < 2048 ? nchunks : 2048;
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL((cumsum_lookback<T>), dim3((unsigned)grid),
-                       dim3(SCAN_THREADS), 0,
-                       reinterpret_cast<hipStream_t>(stream),
-                       static_cast<const T *>(in), in_off, in_stride, n,
-                       static_cast<T *>(out), out_off,
-                       (GU64 *)(agg), (GU64 *)(inc), (GU32 *)(flag),
-                       (GU32 *)(ticket), base);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error(std::string("cumsum_lookback launch: ") +
-                  hipGetErrorString(e));
-        return 1;
-    }
-    return 0;
-}
-
 template <typename T>
 int cumsum_launch(uintptr_t stream, const void *in, int64_t in_off,
                   int64_t in_stride, int64_t n, void *out, int64_t out_off,
@@ -826,50 +655,19 @@ int cumsum_launch(uintptr_t stream, const void *in, int64_t in_off,
     } else {
         return fail("rt_cumsum", "bad phase");
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error(std::string("cumsum launch: ") + hipGetErrorString(e));
-        return 1;
-    }
-    return 0;
+    return launched("cumsum");
 }
 
 }  // namespace
 
-// single-pass decoupled-lookback cumsum.  agg/inc: u64[nchunks] (bit
-// images of T); flag: u32[nchunks] zeroed by the host; ticket: u32[1]
-// zeroed by the host.  dtype: 0=f64 1=f32 2=i64 3=i32.
-extern "C" int rt_cumsum_scan(uintptr_t stream, const void *in,
-                              int64_t in_off, int64_t in_stride, int64_t n,
-                              void *out, int64_t out_off, void *agg,
-                              void *inc, void *flag, void *ticket,
-                              double fbase, int64_t ibase, int dtype) {
-    switch (dtype) {
-        case 0: return cumsum_lookback_launch<double>(
-            stream, in, in_off, in_stride, n, out, out_off, agg, inc, flag,
-            ticket, fbase, ibase);
-        case 1: return cumsum_lookback_launch<float>(
-            stream, in, in_off, in_stride, n, out, out_off, agg, inc, flag,
-            ticket, fbase, ibase);
-        case 2: return cumsum_lookback_launch<int64_t>(
-            stream, in, in_off, in_stride, n, out, out_off, agg, inc, flag,
-            ticket, fbase, ibase);
-        case 3: return cumsum_lookback_launch<int32_t>(
-            stream, in, in_off, in_stride, n, out, out_off, agg, inc, flag,
-            ticket, fbase, ibase);
-        default:
-            set_error("rt_cumsum_scan: bad dtype");
-            return 1;
-    }
-}
-
-// dtype: 0=f64 1=f32 2=i64 3=i32; phase 1/2/3 (see kernel comments)
+// dtype: RT_F64 .. RT_I32; phase 1/2/3 (see kernel comments)
 extern "C" int rt_cumsum(uintptr_t stream, const void *in, int64_t in_off,
                          int64_t in_stride, int64_t n, void *out,
                          int64_t out_off, void *bsums, int64_t nblocks,
                          void *total, double fbase, int64_t ibase,
                          int dtype, int phase) {
-    if (dtype < 0 || dtype > 3) return fail("rt_cumsum", "bad dtype");
+    if (dtype < RT_F64 || dtype > RT_I32)
+        return fail("rt_cumsum", "bad dtype");
     if (phase < 1 || phase > 3) return fail("rt_cumsum", "bad phase");
     if (n < 0) return fail("rt_cumsum", "negative n");
     // phases 1 and 3 use nblocks as their grid (the kernels stride over the
@@ -880,23 +678,11 @@ extern "C" int rt_cumsum(uintptr_t stream, const void *in, int64_t in_off,
     if (!bsums) return fail("rt_cumsum", "NULL bsums");
     if (phase != 2 && !in) return fail("rt_cumsum", "NULL in");
     if (phase == 3 && !out) return fail("rt_cumsum", "NULL out");
-    switch (dtype) {
-        case 0: return cumsum_launch<double>(stream, in, in_off, in_stride, n,
-                                             out, out_off, bsums, nblocks,
-                                             total, fbase, ibase, phase);
-        case 1: return cumsum_launch<float>(stream, in, in_off, in_stride, n,
-                                            out, out_off, bsums, nblocks,
-                                            total, fbase, ibase, phase);
-        case 2: return cumsum_launch<int64_t>(stream, in, in_off, in_stride,
-                                              n, out, out_off, bsums, nblocks,
-                                              total, fbase, ibase, phase);
-        case 3: return cumsum_launch<int32_t>(stream, in, in_off, in_stride,
-                                              n, out, out_off, bsums, nblocks,
-                                              total, fbase, ibase, phase);
-        default:
-            set_error("rt_cumsum: bad dtype");
-            return 1;
-    }
+    return dtype_dispatch<4>("rt_cumsum", dtype, [&](auto t) {
+        return cumsum_launch<decltype(t)>(stream, in, in_off, in_stride, n,
+                                          out, out_off, bsums, nblocks,
+                                          total, fbase, ibase, phase);
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -998,7 +784,6 @@ __global__ __launch_bounds__(256) void mask_write_k(
     // lines: measured 0.58 TB/s).  Thread t owns elements
     // [t*ITEMS, t*ITEMS+ITEMS) of the chunk, so the intra-chunk
     // exclusive scan of per-thread counts preserves C order.
-#define LIDX(x) ((x) + ((x) >> 4))
     __shared__ T vals[MC_CHUNK + SCAN_THREADS];
     __shared__ T outbuf[MC_CHUNK];
     __shared__ unsigned char msk[MC_CHUNK + SCAN_THREADS];
@@ -1043,7 +828,6 @@ __global__ __launch_bounds__(256) void mask_write_k(
             out[obase + k] = outbuf[k];
         __syncthreads();
     }
-#undef LIDX
 }
 
 template <typename T>
@@ -1074,12 +858,7 @@ int mask_compact_launch(uintptr_t stream, const void *a, const void *m,
                            static_cast<T *>(out), g,
                            static_cast<const int64_t *>(bcounts));
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error(std::string("mask_compact launch: ") + hipGetErrorString(e));
-        return 1;
-    }
-    return 0;
+    return launched("mask_compact");
 }
 
 }  // namespace
@@ -1092,7 +871,7 @@ extern "C" int rt_mask_chunk(void) { return MC_CHUNK; }
 // ceil(n / rt_mask_chunk()) int64 slots, 2048-element chunks).  Phase 2 is
 // rt_cumsum(phase=2, dtype=2) on bcounts.  Phase 3: ordered write into
 // dense `out`.  a/m pointers are pre-offset by the caller; strides/shape
-// describe the local box.  dtype: 0=f64 1=f32 2=i64 3=i32 4=i16 5=i8 6=u8.
+// describe the local box.  dtype: any rt_dtype.
 extern "C" int rt_mask_compact(uintptr_t stream, const void *a,
                                const void *m, void *out, int nd,
                                const int64_t *shape,
@@ -1103,7 +882,8 @@ extern "C" int rt_mask_compact(uintptr_t stream, const void *a,
     if (box_extents("rt_mask_compact", nd, 1, shape, a_strides, m_strides,
                     &g.n))
         return 1;
-    if (dtype < 0 || dtype > 6) return fail("rt_mask_compact", "bad dtype");
+    if (dtype < RT_F64 || dtype > RT_U8)
+        return fail("rt_mask_compact", "bad dtype");
     if (phase != 1 && phase != 3)
         return fail("rt_mask_compact", "bad phase (1 or 3; phase 2 is "
                                        "rt_cumsum)");
@@ -1116,35 +896,11 @@ extern "C" int rt_mask_compact(uintptr_t stream, const void *a,
     if (phase == 3 && (!a || !out))
         return fail("rt_mask_compact", "NULL a/out");
     g.nd = nd;
-    for (int d = 0; d < nd; ++d) {
-        g.shape[d] = shape[d];
-        g.astr[d] = a_strides[d];
-        g.mstr[d] = m_strides[d];
-    }
-    for (int d = nd; d < 4; ++d) {
-        g.shape[d] = 1;
-        g.astr[d] = 0;
-        g.mstr[d] = 0;
-    }
-    switch (dtype) {
-        case 0: return mask_compact_launch<double>(stream, a, m, out, g,
-                                                   bcounts, nchunks, phase);
-        case 1: return mask_compact_launch<float>(stream, a, m, out, g,
-                                                  bcounts, nchunks, phase);
-        case 2: return mask_compact_launch<int64_t>(stream, a, m, out, g,
-                                                    bcounts, nchunks, phase);
-        case 3: return mask_compact_launch<int32_t>(stream, a, m, out, g,
-                                                    bcounts, nchunks, phase);
-        case 4: return mask_compact_launch<int16_t>(stream, a, m, out, g,
-                                                    bcounts, nchunks, phase);
-        case 5: return mask_compact_launch<int8_t>(stream, a, m, out, g,
-                                                   bcounts, nchunks, phase);
-        case 6: return mask_compact_launch<uint8_t>(stream, a, m, out, g,
-                                                    bcounts, nchunks, phase);
-        default:
-            set_error("rt_mask_compact: bad dtype");
-            return 1;
-    }
+    fill_geom(nd, shape, g.shape, a_strides, g.astr, m_strides, g.mstr);
+    return dtype_dispatch<7>("rt_mask_compact", dtype, [&](auto t) {
+        return mask_compact_launch<decltype(t)>(stream, a, m, out, g, bcounts,
+                                                nchunks, phase);
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -1320,13 +1076,7 @@ int axis_scan_chunked_launch(uintptr_t stream, const void *in, void *out,
         hipLaunchKernelGGL((axis_scan_ck3<T>), dim3((unsigned)blocks),
                            dim3(256), 0, st, static_cast<T *>(out),
                            static_cast<const T *>(tot2), g, nchunks, clen);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error(std::string("axis_scan chunked launch: ")
-                  + hipGetErrorString(e));
-        return 1;
-    }
-    return 0;
+    return launched("axis_scan chunked");
 }
 
 template <typename T>
@@ -1347,19 +1097,14 @@ int axis_scan_launch(uintptr_t stream, const void *in, void *out,
                            dim3(256), 0, st, static_cast<const T *>(in),
                            static_cast<T *>(out), static_cast<T *>(totals),
                            g);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error(std::string("axis_scan launch: ") + hipGetErrorString(e));
-        return 1;
-    }
-    return 0;
+    return launched("axis_scan");
 }
 
 }  // namespace
 
 // in/out pre-offset to the box origin; shape/strides over the FULL local
 // box (nd dims, nd 2..4); totals: dense C-order slab of the line space.
-// dtype: 0=f64 1=f32 2=i64 3=i32.  nchunks > 1 selects the chunked
+// dtype: RT_F64 .. RT_I32.  nchunks > 1 selects the chunked
 // variant (axis != last with few lines); tot2 then holds
 // nchunks × nlines scratch.
 extern "C" int rt_axis_scan(uintptr_t stream, const void *in, void *out,
@@ -1373,7 +1118,8 @@ extern "C" int rt_axis_scan(uintptr_t stream, const void *in, void *out,
         return 1;
     if (axis < 0 || axis >= nd)
         return fail("rt_axis_scan", "axis out of range");
-    if (dtype < 0 || dtype > 3) return fail("rt_axis_scan", "bad dtype");
+    if (dtype < RT_F64 || dtype > RT_I32)
+        return fail("rt_axis_scan", "bad dtype");
     if (nchunks < 1) return fail("rt_axis_scan", "nchunks < 1");
     if (nchunks > 1 && !tot2)
         return fail("rt_axis_scan", "nchunks > 1 needs tot2");
@@ -1401,35 +1147,14 @@ extern "C" int rt_axis_scan(uintptr_t stream, const void *in, void *out,
     }
     if (nchunks > (1LL << 46) / g.nlines)
         return fail("rt_axis_scan", "nchunks * lines too large");
-    if (nchunks > 1) {
-        switch (dtype) {
-            case 0: return axis_scan_chunked_launch<double>(
-                stream, in, out, totals, tot2, g, nchunks);
-            case 1: return axis_scan_chunked_launch<float>(
-                stream, in, out, totals, tot2, g, nchunks);
-            case 2: return axis_scan_chunked_launch<int64_t>(
-                stream, in, out, totals, tot2, g, nchunks);
-            case 3: return axis_scan_chunked_launch<int32_t>(
-                stream, in, out, totals, tot2, g, nchunks);
-            default:
-                set_error("rt_axis_scan: bad dtype");
-                return 1;
-        }
-    }
     int waves = (axis == nd - 1) ? 1 : 0;
-    switch (dtype) {
-        case 0: return axis_scan_launch<double>(stream, in, out, totals, g,
-                                                waves);
-        case 1: return axis_scan_launch<float>(stream, in, out, totals, g,
-                                               waves);
-        case 2: return axis_scan_launch<int64_t>(stream, in, out, totals, g,
-                                                 waves);
-        case 3: return axis_scan_launch<int32_t>(stream, in, out, totals, g,
-                                                 waves);
-        default:
-            set_error("rt_axis_scan: bad dtype");
-            return 1;
-    }
+    return dtype_dispatch<4>("rt_axis_scan", dtype, [&](auto t) {
+        using T = decltype(t);
+        if (nchunks > 1)
+            return axis_scan_chunked_launch<T>(stream, in, out, totals, tot2,
+                                               g, nchunks);
+        return axis_scan_launch<T>(stream, in, out, totals, g, waves);
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -1520,13 +1245,7 @@ int flat_copy_launch(uintptr_t stream, void *boxed, void *dense,
                                static_cast<T *>(boxed),
                                static_cast<T *>(dense), g.flat0, g.n,
                                g.str[0]);
-        hipError_t e1 = hipGetLastError();
-        if (e1 != hipSuccess) {
-            set_error(std::string("flat_copy launch: ")
-                      + hipGetErrorString(e1));
-            return 1;
-        }
-        return 0;
+        return launched("flat_copy");
     }
     int64_t inner = g.shape[g.nd - 1];
     int64_t rows = (g.n + inner - 1) / inner + 1;
@@ -1547,12 +1266,7 @@ int flat_copy_launch(uintptr_t stream, void *boxed, void *dense,
         hipLaunchKernelGGL((flat_copy_kernel<T, 0>), dim3((unsigned)blocks),
                            dim3(256), 0, st, static_cast<T *>(boxed),
                            static_cast<T *>(dense), g, cpr);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error(std::string("flat_copy launch: ") + hipGetErrorString(e));
-        return 1;
-    }
-    return 0;
+    return launched("flat_copy");
 }
 
 }  // namespace
@@ -1581,15 +1295,7 @@ extern "C" int rt_flat_copy(uintptr_t stream, void *boxed, void *dense,
     g.nd = nd;
     g.n = n;
     g.flat0 = flat0;
-    for (int d = 0; d < nd; ++d) {
-        g.shape[d] = shape[d];
-        g.str[d] = strides[d];
-    }
-    for (int d = nd; d < 4; ++d) {
-        g.shape[d] = 1;
-        g.str[d] = 0;
-    }
-    if (n <= 0) return 0;
+    fill_geom(nd, shape, g.shape, strides, g.str);
     switch (elemsize) {
         case 1: return flat_copy_launch<uint8_t>(stream, boxed, dense, g,
                                                  scatter);
@@ -1848,12 +1554,7 @@ int take_launch(uintptr_t stream, void *dst, const void *src,
                                (uint32_t)re, badp);
         }
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error(std::string("take_rows launch: ") + hipGetErrorString(e));
-        return 1;
-    }
-    return 0;
+    return launched("take_rows");
 }
 
 }  // namespace
@@ -1944,8 +1645,6 @@ namespace {
 // blocks of the flat stage 1 (256 CUs x 8 blocks, the memory-bound grid
 // cap); each block leaves one pair for stage 2
 enum { ARG_GRID_CAP = 2048 };
-
-const int ARG_ESZ[7] = {8, 4, 8, 4, 2, 1, 1};
 
 template <typename T>
 __device__ __forceinline__ T arg_shfl(T v, int d) {
@@ -2155,7 +1854,7 @@ bool arg_flat_vec(const void *in, int64_t in_off, int nd,
 int arg_validate(const char *who, const void *in, int nd,
                  const int64_t *shape, const int64_t *strides, int dtype,
                  int64_t *n_out) {
-    if (dtype < 0 || dtype > 6) {
+    if (dtype < RT_F64 || dtype > RT_U8) {
         set_error(std::string(who) + ": bad dtype");
         return 1;
     }
@@ -2180,15 +1879,6 @@ int arg_validate(const char *who, const void *in, int nd,
         n *= shape[d];
     }
     *n_out = n;
-    return 0;
-}
-
-int arg_launch_status(const char *who) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error(std::string(who) + " launch: " + hipGetErrorString(e));
-        return 1;
-    }
     return 0;
 }
 
@@ -2233,13 +1923,13 @@ int arg_flat_launch(uintptr_t stream, const void *in, int64_t in_off, int nd,
         hipLaunchKernelGGL((arg_flat_s1<T, T>), dim3((unsigned)blocks),
                            dim3(256), 0, st, src, a, static_cast<T *>(sv),
                            static_cast<int64_t *>(si));
-    if (arg_launch_status("rt_arg_flat(1)")) return 1;
+    if (launched("rt_arg_flat(1)")) return 1;
     hipLaunchKernelGGL((arg_flat_s2<T>), dim3(1), dim3(256), 0, st,
                        static_cast<const T *>(sv),
                        static_cast<const int64_t *>(si), (int)blocks,
                        static_cast<T *>(ov), static_cast<int64_t *>(oi),
                        is_max, skipna);
-    return arg_launch_status("rt_arg_flat(2)");
+    return launched("rt_arg_flat(2)");
 }
 
 // -- one axis ----------------------------------------------------------------
@@ -2409,22 +2099,22 @@ int arg_axis_launch(uintptr_t stream, const void *in, int64_t in_off,
             hipLaunchKernelGGL((arg_axis_wave<T, T>),
                                dim3(arg_blocks(a.nout * 64)), dim3(256), 0,
                                st, src, a, outv, outi);
-        return arg_launch_status("rt_arg_axis(wave)");
+        return launched("rt_arg_axis(wave)");
     }
     if (a.C == 1) {
         hipLaunchKernelGGL((arg_axis_thread<T>), dim3(arg_blocks(a.nout)),
                            dim3(256), 0, st, src, a, outv, outi);
-        return arg_launch_status("rt_arg_axis(thread)");
+        return launched("rt_arg_axis(thread)");
     }
     hipLaunchKernelGGL((arg_axis_thread<T>), dim3(arg_blocks(a.nout * a.C)),
                        dim3(256), 0, st, src, a, static_cast<T *>(pv),
                        static_cast<int64_t *>(pi));
-    if (arg_launch_status("rt_arg_axis(chunks)")) return 1;
+    if (launched("rt_arg_axis(chunks)")) return 1;
     hipLaunchKernelGGL((arg_pairs_reduce<T>), dim3(arg_blocks(a.nout)),
                        dim3(256), 0, st, static_cast<const T *>(pv),
                        static_cast<const int64_t *>(pi), a.C, a.nout, outv,
                        outi, a.is_max, a.skipna);
-    return arg_launch_status("rt_arg_axis(pairs)");
+    return launched("rt_arg_axis(pairs)");
 }
 
 // -- pair combine (rt_combine_box for pairs) ----------------------------------
@@ -2471,19 +2161,8 @@ int arg_combine_launch(uintptr_t stream, void *dv, void *di, const void *sv,
                        static_cast<int64_t *>(di) + di_off,
                        static_cast<const T *>(sv),
                        static_cast<const int64_t *>(si), a);
-    return arg_launch_status("rt_arg_combine_box");
+    return launched("rt_arg_combine_box");
 }
-
-#define ARG_DISPATCH(dtype, CALL)                                          \
-    switch (dtype) {                                                       \
-        case 0: return CALL(double);                                       \
-        case 1: return CALL(float);                                        \
-        case 2: return CALL(int64_t);                                      \
-        case 3: return CALL(int32_t);                                      \
-        case 4: return CALL(int16_t);                                      \
-        case 5: return CALL(int8_t);                                       \
-        default: return CALL(uint8_t);                                     \
-    }
 
 }  // namespace
 
@@ -2495,8 +2174,8 @@ extern "C" int rt_arg_flat_regime(const void *in, int64_t in_off, int nd,
     int64_t n;
     if (arg_validate("rt_arg_flat_regime", in, nd, shape, strides, dtype, &n))
         return -1;
-    return arg_flat_vec(in, in_off, nd, shape, strides, ARG_ESZ[dtype]) ? 1
-                                                                        : 0;
+    return arg_flat_vec(in, in_off, nd, shape, strides, dtype_size(dtype))
+               ? 1 : 0;
 }
 
 extern "C" int rt_arg_flat(uintptr_t stream, const void *in, int64_t in_off,
@@ -2512,14 +2191,15 @@ extern "C" int rt_arg_flat(uintptr_t stream, const void *in, int64_t in_off,
         set_error("rt_arg_flat: NULL argument");
         return 1;
     }
-    const bool vec =
-        arg_flat_vec(in, in_off, nd, shape, strides, ARG_ESZ[dtype]);
-#define CALL(T)                                                            \
-    arg_flat_launch<T>(stream, in, in_off, nd, shape, strides, mult, idx0, \
-                       n, vec, is_max != 0, skipna != 0, scratch_vals,     \
-                       scratch_idx, out_val, out_idx)
-    ARG_DISPATCH(dtype, CALL)
-#undef CALL
+    return dtype_dispatch<7>("rt_arg_flat", dtype, [&](auto t) {
+        using T = decltype(t);
+        const bool vec =
+            arg_flat_vec(in, in_off, nd, shape, strides, sizeof(T));
+        return arg_flat_launch<T>(stream, in, in_off, nd, shape, strides,
+                                  mult, idx0, n, vec, is_max != 0,
+                                  skipna != 0, scratch_vals, scratch_idx,
+                                  out_val, out_idx);
+    });
 }
 
 extern "C" int rt_arg_axis(uintptr_t stream, const void *in, int64_t in_off,
@@ -2567,17 +2247,17 @@ extern "C" int rt_arg_axis(uintptr_t stream, const void *in, int64_t in_off,
     }
     // wave regime with 16-byte loads: axis stride 1 and every line start
     // (base + any combination of kept-axis strides) 16-byte aligned
-    const int es = ARG_ESZ[dtype];
-    bool vec = wave && strides[axis] == 1 && shape[axis] >= 16 / es
-        && (reinterpret_cast<uintptr_t>(in) + (uint64_t)(in_off * es)) % 16
-               == 0;
-    for (int d = 0; vec && d < nd - 1; ++d)
-        vec = (strides[d] * es) % 16 == 0;
-#define CALL(T)                                                            \
-    arg_axis_launch<T>(stream, in, in_off, a, wave, vec, part_vals,        \
-                       part_idx, out_vals, out_idx)
-    ARG_DISPATCH(dtype, CALL)
-#undef CALL
+    return dtype_dispatch<7>("rt_arg_axis", dtype, [&](auto t) {
+        using T = decltype(t);
+        const int es = sizeof(T);
+        bool vec = wave && strides[axis] == 1 && shape[axis] >= 16 / es
+            && (reinterpret_cast<uintptr_t>(in) + (uint64_t)(in_off * es))
+                   % 16 == 0;
+        for (int d = 0; vec && d < nd - 1; ++d)
+            vec = (strides[d] * es) % 16 == 0;
+        return arg_axis_launch<T>(stream, in, in_off, a, wave, vec,
+                                  part_vals, part_idx, out_vals, out_idx);
+    });
 }
 
 extern "C" int rt_arg_combine_box(uintptr_t stream, void *dst_vals,
@@ -2609,9 +2289,9 @@ extern "C" int rt_arg_combine_box(uintptr_t stream, void *dst_vals,
         a.dis[d] = d < nd ? dst_idx_strides[d] : 0;
         a.ss[d] = d < nd ? src_strides[d] : 0;
     }
-#define CALL(T)                                                            \
-    arg_combine_launch<T>(stream, dst_vals, dst_idx, src_vals, src_idx,    \
-                          dst_val_off, dst_idx_off, a)
-    ARG_DISPATCH(dtype, CALL)
-#undef CALL
+    return dtype_dispatch<7>("rt_arg_combine_box", dtype, [&](auto t) {
+        return arg_combine_launch<decltype(t)>(stream, dst_vals, dst_idx,
+                                               src_vals, src_idx,
+                                               dst_val_off, dst_idx_off, a);
+    });
 }

@@ -740,7 +740,7 @@ def _fe_mask(ra, h, m):
 @pytest.mark.parametrize("dtype", ["int8", "int16", "bool", "int32",
                                    "float32"])
 def test_frontend_mask_getitem_small_dtypes(ra_gpu, dev, dtype):
-    """a[mask] for the value dtypes behind the _MC_DT mapping."""
+    """a[mask] for the value dtypes behind the RT_DTYPE mapping."""
     M = dev.M
     rng = np.random.default_rng(5)
     for shape in [(M - 1,), (M + 1,), (7, 13, 29)]:

@@ -203,3 +203,13 @@ def test_flat_copy_rejects(lib):
     assert call(n=0) == 0
     assert call(flat0=15, n=0, boxed=None, dense=None) == 0
     assert call(shape=(3, 0), flat0=0, n=0) == 0
+
+
+def test_dtype_table_and_removed_entry(lib):
+    # the binding's dtype codes are the list the GPU kernel tests drive the
+    # C side with; the single-pass lookback scan entry point is gone
+    import rt_ref
+    from ramba_amd import hip_backend
+    assert hip_backend.RT_DTYPE == {
+        **{n: i for i, n in enumerate(rt_ref.DT7)}, "bool": 6}
+    assert not hasattr(lib, "rt_cumsum_scan")

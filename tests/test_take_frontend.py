@@ -11,8 +11,8 @@ import pytest
 
 from conftest import run_both
 
-_MC_DTYPES = ["float64", "float32", "int64", "int32", "int16", "int8",
-              "uint8", "bool"]
+_MASK_DTYPES = ["float64", "float32", "int64", "int32", "int16", "int8",
+                "uint8", "bool"]
 
 
 def _a345(np_):
@@ -129,7 +129,7 @@ class TestIndexKinds:
         _eq(ra, lambda np_: np_.zeros((4, 0, 3))[[1, 2]])
         _eq(ra, lambda np_: _a345(np_)[[1, 2], 2:2])
 
-    @pytest.mark.parametrize("dt", _MC_DTYPES)
+    @pytest.mark.parametrize("dt", _MASK_DTYPES)
     def test_every_dtype(self, ra, dt):
         def impl(np_):
             a = (np_.arange(24) % 5).reshape(6, 4).astype(dt)
