@@ -73,25 +73,22 @@ class AotCompileBackend:
                 and plan.itershape[0] * plan.itershape[1] >= (1 << 16)):
             fams = codegen.find_stencil_families(plan)
             if fams:
-                _, src, _, _, _ = codegen.generate_load_tiled(plan, fams)
-                self._cc(src)
+                self._cc(codegen.generate_load_tiled(plan, fams).source)
         return [np.asarray(ir.reduction_init(s.kind, s.dtype),
                            dtype=s.dtype)[()] for s in plan.reductions]
 
     def axis_reduce_partial(self, bd, off0, strides, lb, axes, kind,
                             out_dtype):
         nd = lb.shape[1]
-        key, src, kname, fields, ls = codegen.generate_axis_reduce(
+        gk = codegen.generate_axis_reduce(
             nd, tuple(sorted(axes)), bd.dtype, out_dtype, kind)
-        self._cc(src)
-        if not ls and len(axes) == 1:
-            key, src, _, _, _ = codegen.generate_axis_reduce(
+        self._cc(gk.source)
+        if not gk.lane_split and len(axes) == 1:
+            self._cc(codegen.generate_axis_reduce(
                 nd, tuple(sorted(axes)), bd.dtype, out_dtype, kind,
-                chunked=True)
-            self._cc(src)
-            key, src, _, _, _ = codegen.generate_axis_reduce(
-                2, (0,), out_dtype, out_dtype, kind)
-            self._cc(src)
+                chunked=True).source)
+            self._cc(codegen.generate_axis_reduce(
+                2, (0,), out_dtype, out_dtype, kind).source)
 
     def fill_container(self, bd, rt, value):
         pass
@@ -259,9 +256,9 @@ def _aot_container_addr(self, bd):
 
 
 def _aot_tiled_kernel(self, desc):
-    key, source, kname, fields = codegen.generate_staged_tiled(desc)
-    self._cc(source)
-    return (key, fields)
+    gk = codegen.generate_staged_tiled(desc)
+    self._cc(gk.source)
+    return gk
 
 
 def _aot_tiled_launch(self, handle, vals, ntiles, red_dtypes=None,

@@ -614,24 +614,128 @@ __device__ __forceinline__ void rt_sincos(double x, double *sr, double *cr) {
 """
 
 
-class GeneratedKernel:
-    """Source + arg-packing recipe for one fused-group structure."""
+class KernelArgs:
+    """A kernel's argument struct, stated once: each adder records a
+    member's C declaration, its name and its `struct` code together.  Every
+    member is 8 bytes, packed little-endian in declaration order."""
 
-    def __init__(self, key, source, kname_main, kname_finish, finish_source,
-                 fields, vec, nd, nred):
+    def __init__(self, sname):
+        self.sname = sname
+        self.members = []     # (C type, name, struct code, fused-kernel src)
+        # set by decl(), when the struct is complete
+        self.struct = None    # struct.Struct over all members
+        self.names = None     # [(name, is double)] for pack()
+        self.srcs = None      # [src] for pack_args' resolution
+
+    def ptr(self, ct, name, restrict=True, src=None):
+        ct += "* __restrict__" if restrict else "*"
+        self.members.append((ct, name, "Q", src))
+
+    def i64(self, name, src=None):
+        self.members.append(("i64", name, "q", src))
+
+    def f64(self, name, src=None):
+        self.members.append(("double", name, "d", src))
+
+    def scalar(self, name, dtype):
+        """A plan scalar: floats travel as double, everything else as i64."""
+        if np.dtype(dtype).kind == "f":
+            self.f64(name, ("scalar_f", name))
+        else:
+            self.i64(name, ("scalar_i", name))
+
+    def view(self, ct, name, bounds=False):
+        """A 2-D view: pointer, element offset, two strides and, with
+        `bounds`, the inclusive box [lo0, hi0] x [lo1, hi1]."""
+        self.ptr(ct, f"{name}_ptr")
+        for f in ("off", "s0", "s1") + (("lo0", "hi0", "lo1", "hi1")
+                                        if bounds else ()):
+            self.i64(f"{name}_{f}")
+
+    def decl(self):
+        """Close the struct: fix the packing layout and return the
+        `struct X { ... };` text, one member per line."""
+        self.struct = struct.Struct(
+            "<" + "".join(c for (_, _, c, _) in self.members))
+        self.names = [(n, c == "d") for (_, n, c, _) in self.members]
+        self.srcs = [s for (_, _, _, s) in self.members]
+        return "\n".join([f"struct {self.sname} {{"]
+                         + [f"  {ct} {n};" for (ct, n, _, _) in self.members]
+                         + ["};"])
+
+    def pack(self, values):
+        """Pack from a name -> value mapping (extra names are ignored)."""
+        return self.struct.pack(*[
+            float(values[n]) if isf else int(values[n])
+            for (n, isf) in self.names])
+
+    def pack_values(self, vals):
+        """Pack a flat value list given in member order."""
+        return self.struct.pack(*vals)
+
+
+class GeneratedKernel:
+    """One generated kernel: source, entry name and argument struct, plus
+    whatever its launch needs.  `kind` selects the backend's launch path:
+    'fused', 'finish', 'axred', 'tiled' or 'lt'."""
+
+    def __init__(self, kind, key, source, kname, args, vec=1, nd=0, nred=0,
+                 anchor=None, yblock=1, finish=None, lane_split=False,
+                 tile=None, fam_meta=None, others=None):
+        self.kind = kind
         self.key = key
         self.source = source
-        self.kname_main = kname_main
-        self.kname_finish = kname_finish
-        self.finish_source = finish_source
-        self.fields = fields     # list of (kind, payload) for packing
+        self.kname = kname
+        self.args = args             # KernelArgs
+        self.handle = None
         self.vec = vec
         self.nd = nd
         self.nred = nred
-        self.handle = None
-        self.finish_handle = None
-        self.anchor = None
-        self.yblock = 1
+        self.anchor = anchor
+        self.yblock = yblock
+        self.finish = finish         # fused reductions: the finish kernel
+        self.lane_split = lane_split
+        self.tile = tile             # load-tiled: (TH, CW, SEG)
+        self.fam_meta = fam_meta     # load-tiled: [(rep, anchor, s0)]
+        self.others = others         # load-tiled: non-family operand names
+
+    @property
+    def finish_source(self):
+        """Source of the finish kernel, or None without reductions."""
+        return self.finish.source if self.finish is not None else None
+
+
+def init_literal(kind, dtype):
+    """C literal of a reduction's identity."""
+    v = ir.reduction_init(kind, dtype)
+    ct = ctype(dtype)
+    if isinstance(v, float) and np.isinf(v):
+        return ("-__builtin_inf()" if v < 0 else "__builtin_inf()") \
+            if ct == "double" else \
+            ("-__builtin_inff()" if v < 0 else "__builtin_inff()")
+    if isinstance(v, bool):
+        return "1" if v else "0"
+    return f"({ct})({v!r})"
+
+
+def comb_expr(comb, dtype, a, b):
+    """C expression combining two partial results of a reduction."""
+    ct = ctype(dtype)
+    if comb == "add":
+        return f"({a}) + ({b})"
+    if comb == "mul":
+        return f"({a}) * ({b})"
+    if comb in ("minimum", "maximum"):
+        lt = "<" if comb == "minimum" else ">"
+        if np.dtype(dtype).kind == "f":
+            return (f"(__builtin_isnan((double)({a})) || (({a}) {lt} "
+                    f"({b}))) ? ({ct})({a}) : ({ct})({b})")
+        return f"(({a}) {lt} ({b})) ? ({ct})({a}) : ({ct})({b})"
+    if comb == "logical_and":
+        return f"((({a}) != 0) && (({b}) != 0)) ? 1 : 0"
+    if comb == "logical_or":
+        return f"((({a}) != 0) || (({b}) != 0)) ? 1 : 0"
+    raise NotImplementedError(comb)
 
 
 def structural_key(plan, classes, vec):
@@ -785,7 +889,7 @@ class KernelGen:
                 ct = ctype(spec.dtype)
                 em.lines.append(
                     f"      acc_{accn} = "
-                    f"{self.comb_expr(comb, spec.dtype, f'acc_{accn}', src)};")
+                    f"{comb_expr(comb, spec.dtype, f'acc_{accn}', src)};")
             else:
                 base, v = tgt.split("@")
                 val = em.emit(expr)
@@ -807,28 +911,7 @@ class KernelGen:
                     f"      a.{self.eff(name)}_p["
                     f"{self.addr_expr(name, inner_expr, row=row)}] = "
                     f"{final};")
-        pad = " " * (indent - 6)
-        return "\n".join(pad + ln.lstrip() if False else
-                         (" " * indent) + ln.strip() for ln in em.lines)
-
-    def comb_expr(self, comb, dtype, a, b):
-        ct = ctype(dtype)
-        if comb == "add":
-            return f"({a}) + ({b})"
-        if comb == "mul":
-            return f"({a}) * ({b})"
-        if comb in ("minimum", "maximum"):
-            lt = "<" if comb == "minimum" else ">"
-            if np.dtype(dtype).kind == "f":
-                return (f"(__builtin_isnan((double)({a})) || (({a}) {lt} "
-                        f"({b}))) ? ({ct})({a}) : ({ct})({b})")
-            return f"(({a}) {lt} ({b})) ? ({ct})({a}) : ({ct})({b})"
-        if comb == "logical_and":
-            return f"((({a}) != 0) && (({b}) != 0)) ? 1 : 0"
-        if comb == "logical_or":
-            return f"((({a}) != 0) || (({b}) != 0)) ? 1 : 0"
-        raise NotImplementedError(comb)
-
+        return "\n".join((" " * indent) + ln.strip() for ln in em.lines)
 
     def emit_quad(self, L, body_ind, tagp, row=None, shared=None):
         """Preloads + per-lane bodies + vector stores for one (x, row)
@@ -840,7 +923,7 @@ class KernelGen:
         V = self.vec
         self.preload = {}
         cse = {} if shared is None else shared
-        nload = self._nload = getattr(self, "_nload", [0])             if shared is not None else [0]
+        nload = self._nload if shared is not None else [0]
 
         def vec_load(name, extra_const):
             parts, const = self.addr_parts(name, "vb", row=row)
@@ -887,52 +970,36 @@ class KernelGen:
 
     # -- full source -----------------------------------------------------------
 
-    def generate(self, key):
+    def generate(self, key, anchor):
         nd, V = self.nd, self.vec
         L = []
         L.append(PREAMBLE)
-        # args struct
-        L.append("struct Args {")
-        fields = []
+        # args struct; each member's `src` is resolved against the plan at
+        # launch (pack_args)
+        A = KernelArgs("Args")
         for d in range(nd):
-            L.append(f"  i64 n{d};")
-            fields.append(("iter_n", d))
+            A.i64(f"n{d}", ("iter_n", d))
         for d in range(nd):
-            L.append(f"  i64 gs{d};")
-            fields.append(("iter_gs", d))
+            A.i64(f"gs{d}", ("iter_gs", d))
         for c in self.class_list:
             if c.base is not None:
                 continue  # folded: shares the base operand's args
-            ct = ctype(c.dtype)
-            L.append(f"  {ct}* __restrict__ {c.name}_p;")
-            fields.append(("ptr", c.name))
-            L.append(f"  i64 {c.name}_off;")
-            fields.append(("off", c.name))
+            A.ptr(ctype(c.dtype), f"{c.name}_p", src=("ptr", c.name))
+            A.i64(f"{c.name}_off", ("off", c.name))
             for d in range(nd - 1):
                 if c.outer_g[d]:
-                    L.append(f"  i64 {c.name}_s{d};")
-                    fields.append(("stride", (c.name, d)))
+                    A.i64(f"{c.name}_s{d}", ("stride", (c.name, d)))
             if c.inner == "g":
-                L.append(f"  i64 {c.name}_sx;")
-                fields.append(("stride", (c.name, nd - 1)))
+                A.i64(f"{c.name}_sx", ("stride", (c.name, nd - 1)))
         for n in sorted(self.plan.scalars):
-            _, dt = self.plan.scalars[n]
-            if np.dtype(dt).kind == "f":
-                L.append(f"  double {n};")
-                fields.append(("scalar_f", n))
-            else:
-                L.append(f"  i64 {n};")
-                fields.append(("scalar_i", n))
+            A.scalar(n, self.plan.scalars[n][1])
         if V > 1:
-            L.append("  i64 lead;")
-            fields.append(("lead", None))
+            A.i64("lead", ("lead", None))
         nred = len(self.plan.reductions)
         if nred:
-            L.append("  char* partials;")
-            fields.append(("partials", None))
-            L.append("  i64 npartials;")
-            fields.append(("npartials", None))
-        L.append("};")
+            A.ptr("char", "partials", restrict=False, src=("partials", None))
+            A.i64("npartials", ("npartials", None))
+        L.append(A.decl())
 
         kname = f"k_{key}"
         L.append(f'extern "C" __global__ void __launch_bounds__(256) '
@@ -940,14 +1007,13 @@ class KernelGen:
         # accumulators
         for spec in self.plan.reductions:
             ct = ctype(spec.dtype)
-            init = self.init_literal(spec)
+            init = init_literal(spec.kind, spec.dtype)
             L.append(f"  {ct} acc_{spec.acc} = {init};")
         # outer loops; nd==2 kernels with row-delta folds use an unrolled
         # y-block so LLVM CSEs the overlapping row vectors across rows
         # (tools/probe_stencil yunroll4: +23% over the flat structure)
         yblock = 4 if (nd == 2 and V > 1
                        and any(c.krow for c in self.class_list)) else 1
-        self.yblock = yblock
         ind = 2
         if nd == 3:
             L.append(f"{' '*ind}for (i64 i0 = blockIdx.z; i0 < a.n0; "
@@ -1040,7 +1106,7 @@ class KernelGen:
                 L.append(f"    for (int o = 32; o > 0; o >>= 1) {{")
                 L.append(f"      {ct} other = {self.shfl_down(spec.dtype, an, 'o')};")
                 L.append(f"      {an} = "
-                         f"{self.comb_expr(comb, spec.dtype, an, 'other')};")
+                         f"{comb_expr(comb, spec.dtype, an, 'other')};")
                 L.append("    }")
                 L.append(f"    __shared__ {ct} lds_{spec.acc}[4];")
                 L.append(f"    if (lane == 0) lds_{spec.acc}[wid] = {an};")
@@ -1054,19 +1120,17 @@ class KernelGen:
                 L.append(f"      {ct} v{ri} = lds_{spec.acc}[0];")
                 for w in range(1, 4):
                     L.append(f"      v{ri} = "
-                             f"{self.comb_expr(comb, spec.dtype, f'v{ri}', f'lds_{spec.acc}[{w}]')};")
+                             f"{comb_expr(comb, spec.dtype, f'v{ri}', f'lds_{spec.acc}[{w}]')};")
                 L.append(f"      *({ct}*)(a.partials + (i64){ri} * "
                          f"a.npartials * 8 + pidx * 8) = v{ri};")
             L.append("    }")
             L.append("  }")
         L.append("}")
 
-        kname_finish = None
-        finish_source = None
-        if nred:
-            kname_finish = f"kf_{key}"
-            finish_source = PREAMBLE + "\n" + self.gen_finish(kname_finish)
-        return "\n".join(L), kname, kname_finish, finish_source, fields
+        return GeneratedKernel(
+            "fused", key, "\n".join(L), kname, A, vec=V, nd=nd, nred=nred,
+            anchor=anchor, yblock=yblock,
+            finish=self.gen_finish(key) if nred else None)
 
     def vec_type(self, dt):
         ct = ctype(dt)
@@ -1087,25 +1151,16 @@ class KernelGen:
             return f"({ct})__shfl_down((int)({var}), {off}, 64)"
         return f"__shfl_down({var}, {off}, 64)"
 
-    def init_literal(self, spec):
-        v = ir.reduction_init(spec.kind, spec.dtype)
-        ct = ctype(spec.dtype)
-        if isinstance(v, float) and np.isinf(v):
-            return ("-__builtin_inf()" if v < 0 else "__builtin_inf()") \
-                if ct == "double" else \
-                ("-__builtin_inff()" if v < 0 else "__builtin_inff()")
-        if isinstance(v, bool):
-            return "1" if v else "0"
-        return f"({ct})({v!r})"
-
-    def gen_finish(self, kname):
+    def gen_finish(self, key):
         """One-block finish kernel folding the per-workgroup partials into
         per-rank outputs (device scalars)."""
-        L = []
-        L.append("struct FArgs { char* partials; i64 npartials; "
-                 + " ".join(f"char* out{i};" for i in
-                            range(len(self.plan.reductions)))
-                 + " };")
+        kname = f"kf_{key}"
+        A = KernelArgs("FArgs")
+        A.ptr("char", "partials", restrict=False)
+        A.i64("npartials")
+        for i in range(len(self.plan.reductions)):
+            A.ptr("char", f"out{i}", restrict=False)
+        L = [PREAMBLE, A.decl()]
         L.append(f'extern "C" __global__ void __launch_bounds__(256) '
                  f"{kname}(FArgs f) {{")
         L.append("  const int lane = threadIdx.x & 63;")
@@ -1113,18 +1168,18 @@ class KernelGen:
         for ri, spec in enumerate(self.plan.reductions):
             ct = ctype(spec.dtype)
             comb, _ = ir.REDUCTIONS[spec.kind]
-            init = self.init_literal(spec)
+            init = init_literal(spec.kind, spec.dtype)
             L.append(f"  {{")
             L.append(f"    {ct} acc = {init};")
             L.append(f"    for (i64 i = threadIdx.x; i < f.npartials; "
                      f"i += 256) {{")
             L.append(f"      {ct} pv = *({ct}*)(f.partials + (i64){ri} * "
                      f"f.npartials * 8 + i * 8);")
-            L.append(f"      acc = {self.comb_expr(comb, spec.dtype, 'acc', 'pv')};")
+            L.append(f"      acc = {comb_expr(comb, spec.dtype, 'acc', 'pv')};")
             L.append("    }")
             L.append("    for (int o = 32; o > 0; o >>= 1) {")
             L.append(f"      {ct} other = {self.shfl_down(spec.dtype, 'acc', 'o')};")
-            L.append(f"      acc = {self.comb_expr(comb, spec.dtype, 'acc', 'other')};")
+            L.append(f"      acc = {comb_expr(comb, spec.dtype, 'acc', 'other')};")
             L.append("    }")
             L.append(f"    __shared__ {ct} lds[4];")
             L.append("    if (lane == 0) lds[wid] = acc;")
@@ -1132,13 +1187,13 @@ class KernelGen:
             L.append("    if (threadIdx.x == 0) {")
             L.append(f"      {ct} v = lds[0];")
             for w in range(1, 4):
-                L.append(f"      v = {self.comb_expr(comb, spec.dtype, 'v', f'lds[{w}]')};")
+                L.append(f"      v = {comb_expr(comb, spec.dtype, 'v', f'lds[{w}]')};")
             L.append(f"      *({ct}*)f.out{ri} = v;")
             L.append("    }")
             L.append("    __syncthreads();")
             L.append("  }")
         L.append("}")
-        return "\n".join(L)
+        return GeneratedKernel("finish", key + "_f", "\n".join(L), kname, A)
 
 
 def decide_vec(plan):
@@ -1155,34 +1210,22 @@ def generate(plan):
         raise NotImplementedError(f"{nd}-d iteration spaces (shardview is "
                                   "<=4-D, SURVEY §8 a8)")
     vec, classes, anchor, key = plan_structure(plan)
-    gen = KernelGen(plan, classes, vec)
-    source, kmain, kfinish, finish_source, fields = gen.generate(key)
-    gk = GeneratedKernel(key, source, kmain, kfinish, finish_source,
-                         fields, vec, nd, len(plan.reductions))
-    gk.anchor = anchor
-    gk.yblock = getattr(gen, "yblock", 1)
-    return gk
+    return KernelGen(plan, classes, vec).generate(key, anchor)
 
 
 def pack_args(gk, plan, ptr_of):
-    """Pack the Args struct per gk.fields (one struct.pack call; the
-    format string is cached on the kernel).  ptr_of(name) -> device
-    address of an operand buffer; special names '__partials__'."""
+    """Pack the fused kernel's Args: every member's `src` resolved against
+    the plan into one flat list, then one pack.  ptr_of(name) -> device
+    address of an operand buffer; special names '__partials__' and
+    '__npartials__'."""
     opmap = {o.name: o for o in plan.operands}
     lead = 0
     if gk.anchor is not None and gk.vec > 1:
         lead = (-opmap[gk.anchor].offset0) % gk.vec
-    fmt = getattr(gk, "_pack_fmt", None)
-    if fmt is None:
-        codes = {"iter_n": "q", "iter_gs": "q", "ptr": "Q", "off": "q",
-                 "stride": "q", "scalar_f": "d", "scalar_i": "q",
-                 "lead": "q", "partials": "Q", "npartials": "q"}
-        fmt = "<" + "".join(codes[k] for (k, _) in gk.fields)
-        gk._pack_fmt = fmt
     vals = []
     ap = vals.append
     scalars = plan.scalars
-    for kind, payload in gk.fields:
+    for kind, payload in gk.args.srcs:
         if kind == "iter_n":
             ap(plan.itershape[payload])
         elif kind == "iter_gs":
@@ -1206,16 +1249,7 @@ def pack_args(gk, plan, ptr_of):
             ap(ptr_of("__npartials__"))
         else:
             raise AssertionError(kind)
-    return struct.pack(fmt, *vals)
-
-
-def pack_finish_args(partials_ptr, npartials, out_ptrs):
-    out = bytearray()
-    out += struct.pack("<Q", partials_ptr)
-    out += struct.pack("<q", npartials)
-    for p in out_ptrs:
-        out += struct.pack("<Q", p)
-    return bytes(out)
+    return gk.args.pack_values(vals)
 
 
 # ---------------------------------------------------------------------------
@@ -1235,9 +1269,9 @@ def generate_axis_reduce(nd, axes, in_dtype, out_dtype, kind,
       lanes split the innermost reduction (coalesced), `__shfl_down` tree
       combines (the wave idiom of the CDNA4 guide, Appendix B).
 
-    Args struct (packed by pack_axis_reduce_args):
-      i64 oe{j} for each out axis (out extents, in axis order)
-      i64 ke{j} for each reduced axis (extents)
+    AxArgs members:
+      i64 oe{j} for the j-th kept axis (out extents, in axis order)
+      i64 ke{j} for the j-th reduced axis (extents, in axis order)
       T* in; i64 in_off; i64 in_s{d} for every view axis d
       O* out  (contiguous over out extents, row-major)
     """
@@ -1249,47 +1283,24 @@ def generate_axis_reduce(nd, axes, in_dtype, out_dtype, kind,
     lane_split = (nd - 1) in axes
     assert not (chunked and (lane_split or len(axes) != 1))
 
-    def combc(a, b):
-        if comb == "add":
-            return f"({a}) + ({b})"
-        if comb == "mul":
-            return f"({a}) * ({b})"
-        if comb in ("minimum", "maximum"):
-            lt = "<" if comb == "minimum" else ">"
-            if np.dtype(out_dtype).kind == "f":
-                return (f"(__builtin_isnan((double)({a})) || (({a}) {lt} "
-                        f"({b}))) ? ({ot})({a}) : ({ot})({b})")
-            return f"(({a}) {lt} ({b})) ? ({ot})({a}) : ({ot})({b})"
-        if comb == "logical_and":
-            return f"((({a}) != 0) && (({b}) != 0)) ? 1 : 0"
-        return f"((({a}) != 0) || (({b}) != 0)) ? 1 : 0"
-
-    init = _axinit(kind, out_dtype)
-    L = [PREAMBLE]
-    L.append("struct AxArgs {")
-    fields = []
-    for j, d in enumerate(out_axes):
-        L.append(f"  i64 oe{j};")
-        fields.append(("oe", d))
-    for j, d in enumerate(axes):
-        L.append(f"  i64 ke{j};")
-        fields.append(("ke", d))
-    L.append(f"  {it}* __restrict__ in;")
-    fields.append(("in_ptr", None))
-    L.append("  i64 in_off;")
-    fields.append(("in_off", None))
+    init = init_literal(kind, out_dtype)
+    A = KernelArgs("AxArgs")
+    for j in range(len(out_axes)):
+        A.i64(f"oe{j}")
+    for j in range(len(axes)):
+        A.i64(f"ke{j}")
+    A.ptr(it, "in")
+    A.i64("in_off")
     for d in range(nd):
-        L.append(f"  i64 in_s{d};")
-        fields.append(("in_s", d))
-    L.append(f"  {ot}* __restrict__ out;")
-    fields.append(("out_ptr", None))
+        A.i64(f"in_s{d}")
+    A.ptr(ot, "out")
     if chunked:
         # split the (single) reduced axis into nchunk ragged chunks of
         # clen; chunk is an extra slowest OUT axis (parallelism for
         # small-nout reductions like sum(axis=0))
-        L.append("  i64 nchunk; i64 clen; i64 ktot;")
-        fields.append(("chunk", None))
-    L.append("};")
+        for n in ("nchunk", "clen", "ktot"):
+            A.i64(n)
+    L = [PREAMBLE, A.decl()]
 
     key = hashlib.sha256(
         f"axred:{nd}:{axes}:{in_dtype}:{out_dtype}:{kind}:{chunked}"
@@ -1340,7 +1351,7 @@ def generate_axis_reduce(nd, axes, in_dtype, out_dtype, kind,
         else:
             L.append(f"{ind}  {ot} v = ({ot})a.in[{addr} + kk * "
                      f"a.in_s{inner}];")
-        L.append(f"{ind}  acc = {combc('acc', 'v')};")
+        L.append(f"{ind}  acc = {comb_expr(comb, out_dtype, 'acc', 'v')};")
         L.append(f"{ind}}}")
         for j in range(len(outer_red)):
             ind = ind[:-2]
@@ -1351,7 +1362,7 @@ def generate_axis_reduce(nd, axes, in_dtype, out_dtype, kind,
             L.append(f"      {ot} other = ({ot})__shfl_down((int)acc, off, 64);")
         else:
             L.append(f"      {ot} other = __shfl_down(acc, off, 64);")
-        L.append(f"      acc = {combc('acc', 'other')};")
+        L.append(f"      acc = {comb_expr(comb, out_dtype, 'acc', 'other')};")
         L.append("    }")
         L.append("    if (lane == 0) a.out[w] = acc;")
     elif chunked:
@@ -1365,7 +1376,7 @@ def generate_axis_reduce(nd, axes, in_dtype, out_dtype, kind,
                      "? 1 : 0;")
         else:
             L.append(f"      {ot} v = ({ot})a.in[base + kk * a.in_s{d}];")
-        L.append(f"      acc = {combc('acc', 'v')};")
+        L.append(f"      acc = {comb_expr(comb, out_dtype, 'acc', 'v')};")
         L.append("    }")
         L.append("    a.out[o] = acc;")
     else:
@@ -1379,49 +1390,15 @@ def generate_axis_reduce(nd, axes, in_dtype, out_dtype, kind,
             L.append(f"{ind}{ot} v = (a.in[{addr}] != 0) ? 1 : 0;")
         else:
             L.append(f"{ind}{ot} v = ({ot})a.in[{addr}];")
-        L.append(f"{ind}acc = {combc('acc', 'v')};")
+        L.append(f"{ind}acc = {comb_expr(comb, out_dtype, 'acc', 'v')};")
         for j in range(len(axes)):
             ind = ind[:-2]
             L.append(f"{ind}}}")
         L.append("    a.out[o] = acc;")
     L.append("  }")
     L.append("}")
-    return key, "\n".join(L), kname, fields, lane_split
-
-
-def _axinit(kind, dtype):
-    v = ir.reduction_init(kind, dtype)
-    ct = ctype(dtype)
-    if isinstance(v, float) and np.isinf(v):
-        return ("-__builtin_inf()" if v < 0 else "__builtin_inf()") \
-            if ct == "double" else \
-            ("-__builtin_inff()" if v < 0 else "__builtin_inff()")
-    if isinstance(v, bool):
-        return "1" if v else "0"
-    return f"({ct})({v!r})"
-
-
-def pack_axis_reduce_args(fields, out_extents_by_axis, red_extents_by_axis,
-                          in_ptr, in_off, in_strides, out_ptr,
-                          chunk_spec=None):
-    out = bytearray()
-    for kind, d in fields:
-        if kind == "oe":
-            out += struct.pack("<q", out_extents_by_axis[d])
-        elif kind == "ke":
-            out += struct.pack("<q", red_extents_by_axis[d])
-        elif kind == "in_ptr":
-            out += struct.pack("<Q", in_ptr)
-        elif kind == "in_off":
-            out += struct.pack("<q", in_off)
-        elif kind == "in_s":
-            out += struct.pack("<q", in_strides[d])
-        elif kind == "out_ptr":
-            out += struct.pack("<Q", out_ptr)
-        elif kind == "chunk":
-            nchunk, clen, ktot = chunk_spec
-            out += struct.pack("<qqq", nchunk, clen, ktot)
-    return bytes(out)
+    return GeneratedKernel("axred", key, "\n".join(L), kname, A,
+                           lane_split=lane_split)
 
 
 # ---------------------------------------------------------------------------
@@ -1488,7 +1465,7 @@ def staged_tiled_key(desc):
 
 
 def generate_staged_tiled(desc):
-    """desc (structural only; runtime values go through the fields):
+    """desc (structural only; runtime values go through TkArgs):
       s1_stmts, s2_stmts : lists of ir.Assign (stage1 names p_-prefixed)
       staged : [(lds, dtype, live)]  # one per staged gid, emit order;
                `lds` is also the stage-1 var base name (p_<writer var>)
@@ -1497,7 +1474,6 @@ def generate_staged_tiled(desc):
       s2_ops : [(var, dtype, written)]
       scalars : {name: np.dtype}     # merged, stage-1 names p_-prefixed
       E0, E1 : global footprint extents (>= all reader deltas)
-    returns (key, source, kname, fields): fields = ordered packing names.
     """
     E0, E1 = desc["E0"], desc["E1"]
     TH = int(os.environ.get("RAMBA_TK_TH", str(TILE_H)))
@@ -1509,63 +1485,34 @@ def generate_staged_tiled(desc):
     key = staged_tiled_key(desc)
     kname = f"tk_{key}"
 
-    fields = [("n0", "q"), ("n1", "q"), ("gs0", "q"), ("gs1", "q"),
-              ("gb0", "q"), ("gb1", "q"), ("N0", "q"), ("N1", "q")]
-    L = [PREAMBLE]
-    L.append("struct TkArgs {")
-    L.append("  i64 n0, n1;      // consumer exec-box extents")
-    L.append("  i64 gs0, gs1;    // consumer global start (Iota)")
-    L.append("  i64 gb0, gb1;    // base coord of footprint origin at k=0")
-    L.append("  i64 N0, N1;      // producer-array global shape")
+    A = KernelArgs("TkArgs")
+    for n in ("n0", "n1",       # consumer exec-box extents
+              "gs0", "gs1",     # consumer global start (Iota)
+              "gb0", "gb1",     # base coord of footprint origin at k=0
+              "N0", "N1"):      # producer-array global shape
+        A.i64(n)
     for (lds, dt, live) in desc["staged"]:
         if live:
-            for f in (f"{lds}_ptr", f"{lds}_off", f"{lds}_s0", f"{lds}_s1",
-                      f"{lds}_lo0", f"{lds}_hi0", f"{lds}_lo1",
-                      f"{lds}_hi1"):
-                fields.append((f, "Q" if f.endswith("ptr") else "q"))
-            L.append(f"  {ctype(dt)}* __restrict__ {lds}_ptr; "
-                     f"i64 {lds}_off, {lds}_s0, {lds}_s1, "
-                     f"{lds}_lo0, {lds}_hi0, {lds}_lo1, {lds}_hi1;")
+            A.view(ctype(dt), lds, bounds=True)
     for (var, dt) in desc["s1_stores"]:
-        for f in (f"{var}_ptr", f"{var}_off", f"{var}_s0", f"{var}_s1",
-                  f"{var}_lo0", f"{var}_hi0", f"{var}_lo1", f"{var}_hi1"):
-            fields.append((f, "Q" if f.endswith("ptr") else "q"))
-        L.append(f"  {ctype(dt)}* __restrict__ {var}_ptr; "
-                 f"i64 {var}_off, {var}_s0, {var}_s1, "
-                 f"{var}_lo0, {var}_hi0, {var}_lo1, {var}_hi1;")
+        A.view(ctype(dt), var, bounds=True)
     for (var, dt, written) in desc["s2_ops"]:
-        for f in (f"{var}_ptr", f"{var}_off", f"{var}_s0", f"{var}_s1"):
-            fields.append((f, "Q" if f.endswith("ptr") else "q"))
-        L.append(f"  {ctype(dt)}* __restrict__ {var}_ptr; "
-                 f"i64 {var}_off, {var}_s0, {var}_s1;")
+        A.view(ctype(dt), var)
     for n in sorted(desc["scalars"]):
-        dt = desc["scalars"][n]
-        if np.dtype(dt).kind == "f":
-            fields.append((n, "d"))
-            L.append(f"  double {n};")
-        else:
-            fields.append((n, "q"))
-            L.append(f"  i64 {n};")
+        A.scalar(n, desc["scalars"][n])
     tk_reds = desc.get("tk_reds", [])
     for ri, (wvar, dt) in enumerate(tk_reds):
-        L.append(f"  {ctype(dt)}* __restrict__ red{ri}_ptr;")
-        fields.append((f"red{ri}_ptr", "Q"))
+        A.ptr(ctype(dt), f"red{ri}_ptr")
         # base-coordinate addressing of the reduction SOURCE array + up
         # to 4 rim boxes (core minus written image): the kernel folds
         # the unwritten rim cells into the same partials, so the fused
         # sum needs no extra launches at all
-        L.append(f"  {ctype(dt)}* __restrict__ rsrc{ri}_ptr; "
-                 f"i64 rsrc{ri}_off, rsrc{ri}_s0, rsrc{ri}_s1, "
-                 f"rim{ri}_n;")
-        fields += [(f"rsrc{ri}_ptr", "Q"), (f"rsrc{ri}_off", "q"),
-                   (f"rsrc{ri}_s0", "q"), (f"rsrc{ri}_s1", "q"),
-                   (f"rim{ri}_n", "q")]
+        A.view(ctype(dt), f"rsrc{ri}")
+        A.i64(f"rim{ri}_n")
         for k in range(4):
-            L.append(f"  i64 rim{ri}_{k}_lo0, rim{ri}_{k}_hi0, "
-                     f"rim{ri}_{k}_lo1, rim{ri}_{k}_hi1;")
-            fields += [(f"rim{ri}_{k}_lo0", "q"), (f"rim{ri}_{k}_hi0", "q"),
-                       (f"rim{ri}_{k}_lo1", "q"), (f"rim{ri}_{k}_hi1", "q")]
-    L.append("};")
+            for f in ("lo0", "hi0", "lo1", "hi1"):
+                A.i64(f"rim{ri}_{k}_{f}")
+    L = [PREAMBLE, A.decl()]
 
     L.append(f'extern "C" __global__ void __launch_bounds__(256) '
              f"{kname}(TkArgs a) {{")
@@ -1712,24 +1659,7 @@ def generate_staged_tiled(desc):
         L.append("    }")
         L.append("  }")
     L.append("}")
-    return key, "\n".join(L), kname, fields
-
-
-_TK_FMT_CACHE = {}
-
-
-def pack_tk_args(fields, values):
-    fid = id(fields)
-    ent = _TK_FMT_CACHE.get(fid)
-    if ent is None or ent[0] is not fields:
-        fmt = "<" + "".join(k for (_, k) in fields)
-        if len(_TK_FMT_CACHE) > 512:
-            _TK_FMT_CACHE.clear()
-        _TK_FMT_CACHE[fid] = ent = (fields, fmt)
-    fmt = ent[1]
-    return struct.pack(fmt, *[
-        float(values[n]) if k == "d" else int(values[n])
-        for (n, k) in fields])
+    return GeneratedKernel("tiled", key, "\n".join(L), kname, A)
 
 
 # ---------------------------------------------------------------------------
@@ -1845,29 +1775,18 @@ def generate_load_tiled(plan, fams):
         TH, NCH, V, SEG)).encode()).hexdigest()[:24]
     kname = f"lt_{key}"
 
-    fields = [("n0", "q"), ("n1", "q"), ("gs0", "q"), ("gs1", "q")]
-    L = [PREAMBLE]
-    L.append("struct LtArgs {")
-    L.append("  i64 n0, n1, gs0, gs1;")
+    A = KernelArgs("LtArgs")
+    for n in ("n0", "n1", "gs0", "gs1"):
+        A.i64(n)
     for fi, (anchor, s0, dt, mem, rep) in enumerate(fams):
-        L.append(f"  {ctype(dt)}* __restrict__ fam{fi}_ptr; "
-                 f"i64 fam{fi}_off, fam{fi}_s0;")
-        fields += [(f"fam{fi}_ptr", "Q"), (f"fam{fi}_off", "q"),
-                   (f"fam{fi}_s0", "q")]
+        A.ptr(ctype(dt), f"fam{fi}_ptr")
+        A.i64(f"fam{fi}_off")
+        A.i64(f"fam{fi}_s0")
     for o in other_ops:
-        L.append(f"  {ctype(o.dtype)}* __restrict__ {o.name}_ptr; "
-                 f"i64 {o.name}_off, {o.name}_s0, {o.name}_s1;")
-        fields += [(f"{o.name}_ptr", "Q"), (f"{o.name}_off", "q"),
-                   (f"{o.name}_s0", "q"), (f"{o.name}_s1", "q")]
+        A.view(ctype(o.dtype), o.name)
     for n in sorted(plan.scalars):
-        dt = plan.scalars[n][1]
-        if np.dtype(dt).kind == "f":
-            fields.append((n, "d"))
-            L.append(f"  double {n};")
-        else:
-            fields.append((n, "q"))
-            L.append(f"  i64 {n};")
-    L.append("};")
+        A.scalar(n, plan.scalars[n][1])
+    L = [PREAMBLE, A.decl()]
 
     L.append(f'extern "C" __global__ void __launch_bounds__(256) '
              f"{kname}(LtArgs a) {{")
@@ -2020,4 +1939,7 @@ def generate_load_tiled(plan, fams):
     L.append("    }")
     L.append("  }")
     L.append("}")
-    return key, "\n".join(L), kname, fields, (TH, CW, SEG)
+    return GeneratedKernel(
+        "lt", key, "\n".join(L), kname, A, tile=(TH, CW, SEG),
+        fam_meta=[(rep, anchor, s0) for (anchor, s0, dt, mem, rep) in fams],
+        others=[o.name for o in other_ops])

@@ -377,30 +377,46 @@ class HipBackend:
 
     # -- kernel execution -------------------------------------------------------
 
+    def _compile(self, gk, what):
+        """rt_kernel_get for `gk` (and its finish kernel): sets the handles."""
+        if int(os.environ.get("RAMBA_SHOW_CODE", "0")):
+            print(f"=== {what} kernel {gk.key} ===\n{gk.source}\n",
+                  flush=True)
+        h = ctypes.c_void_p()
+        self._check(self.lib.rt_kernel_get(
+            gk.key.encode(), gk.source.encode(), gk.kname.encode(),
+            ctypes.byref(h)), f"rt_kernel_get({what})")
+        gk.handle = h.value
+        if gk.finish is not None:
+            self._compile(gk.finish, "finish")
+        return gk
+
+    def _launch(self, gk, grid, args, what, timed=True):
+        """The one rt_launch; with time_kernels, `timed` launches are
+        bracketed by an event pair and logged under the kernel's key."""
+        timed = timed and self.time_kernels
+        if timed:
+            ev0 = self.torch.cuda.Event(enable_timing=True)
+            ev1 = self.torch.cuda.Event(enable_timing=True)
+            ev0.record()
+        self._check(self.lib.rt_launch(
+            ctypes.c_void_p(gk.handle), grid[0], grid[1], grid[2], 256,
+            self._stream(), args, len(args)), f"rt_launch({what})")
+        if timed:
+            ev1.record()
+            ev1.synchronize()
+            self.kernel_times_ms.append(ev0.elapsed_time(ev1))
+            self.kernel_keys.append(gk.key)
+
     def _get_kernel(self, plan):
         # fast path: structural key without source generation
         vec, classes, anchor, key = codegen.plan_structure(plan)
         cached = self.kernels.get(key)
-        if cached is not None:
-            return cached
-        gk = codegen.generate(plan)
-        assert gk.key == key
-        if int(os.environ.get("RAMBA_SHOW_CODE", "0")):
-            print(f"=== kernel {gk.key} ===\n{gk.source}\n", flush=True)
-        h = ctypes.c_void_p()
-        self._check(self.lib.rt_kernel_get(
-            gk.key.encode(), gk.source.encode(), gk.kname_main.encode(),
-            ctypes.byref(h)), "rt_kernel_get")
-        gk.handle = h.value
-        if gk.kname_finish:
-            hf = ctypes.c_void_p()
-            self._check(self.lib.rt_kernel_get(
-                (gk.key + "_f").encode(), gk.finish_source.encode(),
-                gk.kname_finish.encode(), ctypes.byref(hf)),
-                "rt_kernel_get(finish)")
-            gk.finish_handle = hf.value
-        self.kernels[gk.key] = gk
-        return gk
+        if cached is None:
+            cached = self._compile(codegen.generate(plan), "fused")
+            assert cached.key == key
+            self.kernels[key] = cached
+        return cached
 
     def launch(self, plan, recipe=None):
         ntiming = common.ntiming
@@ -411,18 +427,18 @@ class HipBackend:
             gk = self._maybe_load_tiled(plan) or self._get_kernel(plan)
             if recipe is not None:
                 recipe.backend_kernel = gk
-        if isinstance(gk, tuple) and gk[0] == "lt":
-            r = self._launch_load_tiled(gk, plan)
+        if gk.kind == "lt":
+            self._launch_load_tiled(gk, plan)
             if ntiming:
                 add_time("hb_submit", _time.perf_counter() - _t0)
-            return r
+            return []
         nd = gk.nd
         shape = plan.itershape
         V = gk.vec
         nx = shape[nd - 1]
         cap = int(os.environ.get("RAMBA_GRID_CAP", "32768"))
         gx = max(1, min(cap, (nx + 256 * V - 1) // (256 * V)))
-        yb = getattr(gk, "yblock", 1)
+        yb = gk.yblock
         gy = max(1, min(8192, (shape[nd - 2] + yb - 1) // yb)) \
             if nd >= 2 else 1
         if nd == 3:
@@ -461,27 +477,15 @@ class HipBackend:
         if ntiming:
             add_time("hb_prep", _time.perf_counter() - _t0)
             _t0 = _time.perf_counter()
-        stream = self._stream()
-        if self.time_kernels:
-            ev0 = self.torch.cuda.Event(enable_timing=True)
-            ev1 = self.torch.cuda.Event(enable_timing=True)
-            ev0.record()
-        self._check(self.lib.rt_launch(
-            ctypes.c_void_p(gk.handle), gx, gy, gz, 256, stream, args,
-            len(args)), "rt_launch")
-        if self.time_kernels:
-            ev1.record()
-            ev1.synchronize()
-            self.kernel_times_ms.append(ev0.elapsed_time(ev1))
-            self.kernel_keys.append(gk.key)
+        self._launch(gk, (gx, gy, gz), args, "fused")
         results = []
         if gk.nred:
-            fargs = codegen.pack_finish_args(
-                partials.data_ptr(), np_partials,
-                [o.data_ptr() for o in outs])
-            self._check(self.lib.rt_launch(
-                ctypes.c_void_p(gk.finish_handle), 1, 1, 1, 256, stream,
-                fargs, len(fargs)), "rt_launch(finish)")
+            fvals = {"partials": partials.data_ptr(),
+                     "npartials": np_partials}
+            for i, o in enumerate(outs):
+                fvals[f"out{i}"] = o.data_ptr()
+            self._launch(gk.finish, (1, 1, 1), gk.finish.args.pack(fvals),
+                         "finish", timed=False)
             for spec, o in zip(plan.reductions, outs):
                 v = o.cpu().numpy()[0]
                 results.append(np.asarray(v, dtype=spec.dtype)[()])
@@ -505,35 +509,32 @@ class HipBackend:
 
     def _hb_axred_kernel(self, nd, axes, in_dtype, out_dtype, kind,
                          chunked=False):
-        from . import codegen as cg
         ck = ("axred", nd, tuple(sorted(axes)), str(in_dtype), str(out_dtype),
               kind, chunked)
         cached = self.kernels.get(ck)
         if cached is None:
-            key, source, kname, fields, lane_split = cg.generate_axis_reduce(
-                nd, axes, in_dtype, out_dtype, kind, chunked=chunked)
-            h = ctypes.c_void_p()
-            self._check(self.lib.rt_kernel_get(
-                key.encode(), source.encode(), kname.encode(),
-                ctypes.byref(h)), "rt_kernel_get(axred)")
-            cached = (h.value, fields, lane_split)
-            self.kernels[ck] = cached
+            cached = self.kernels[ck] = self._compile(
+                codegen.generate_axis_reduce(nd, axes, in_dtype, out_dtype,
+                                             kind, chunked=chunked), "axred")
         return cached
 
-    def _hb_axred_launch(self, handle, fields, lane_split, out_extents,
-                         red_extents, in_ptr, in_off, in_strides, out_ptr,
-                         nout, chunk_spec=None):
-        from . import codegen as cg
-        args = cg.pack_axis_reduce_args(fields, out_extents, red_extents,
-                                        in_ptr, in_off, in_strides, out_ptr,
-                                        chunk_spec=chunk_spec)
-        if lane_split:
+    def _hb_axred_launch(self, gk, out_extents, red_extents, in_ptr, in_off,
+                         in_strides, out_ptr, nout, chunk_spec=None):
+        vals = {"in": in_ptr, "in_off": in_off, "out": out_ptr}
+        for j, d in enumerate(sorted(out_extents)):
+            vals[f"oe{j}"] = out_extents[d]
+        for j, d in enumerate(sorted(red_extents)):
+            vals[f"ke{j}"] = red_extents[d]
+        for d, s in enumerate(in_strides):
+            vals[f"in_s{d}"] = s
+        if chunk_spec is not None:
+            vals["nchunk"], vals["clen"], vals["ktot"] = chunk_spec
+        if gk.lane_split:
             gx = max(1, min(4096, (nout * 64 + 255) // 256))
         else:
             gx = max(1, min(4096, (nout + 255) // 256))
-        self._check(self.lib.rt_launch(
-            ctypes.c_void_p(handle), gx, 1, 1, 256, self._stream(), args,
-            len(args)), "rt_launch(axred)")
+        self._launch(gk, (gx, 1, 1), gk.args.pack(vals), "axred",
+                     timed=False)
 
     def axis_reduce_partial(self, bd, off0, strides, lb, axes, kind,
                             out_dtype):
@@ -566,24 +567,21 @@ class HipBackend:
             part = self.torch.empty((C, nout), dtype=self._tdt(out_dtype),
                                     device="cuda")
             self.temps["__axred_s1__"] = part
-            h1, f1, _ = self._hb_axred_kernel(nd, axes, bd.dtype, out_dtype,
-                                              kind, chunked=True)
-            self._hb_axred_launch(h1, f1, False, out_extents, red_extents,
+            k1 = self._hb_axred_kernel(nd, axes, bd.dtype, out_dtype, kind,
+                                       chunked=True)
+            self._hb_axred_launch(k1, out_extents, red_extents,
                                   self._cont(bd).data_ptr(), off0, strides,
                                   part.data_ptr(), nout * C,
                                   chunk_spec=(C, clen, K))
             # stage 2: reduce the chunk axis of the contiguous (C, nout) temp
-            h2, f2, ls2 = self._hb_axred_kernel(2, (0,), out_dtype, out_dtype,
-                                                kind)
-            self._hb_axred_launch(h2, f2, ls2, {1: nout}, {0: C},
-                                  part.data_ptr(), 0, (nout, 1),
-                                  out_t.data_ptr(), nout)
+            k2 = self._hb_axred_kernel(2, (0,), out_dtype, out_dtype, kind)
+            self._hb_axred_launch(k2, {1: nout}, {0: C}, part.data_ptr(), 0,
+                                  (nout, 1), out_t.data_ptr(), nout)
             return
-        handle, fields, lane_split = self._hb_axred_kernel(
-            nd, axes, bd.dtype, out_dtype, kind)
-        self._hb_axred_launch(handle, fields, lane_split, out_extents,
-                              red_extents, self._cont(bd).data_ptr(), off0,
-                              strides, out_t.data_ptr(), nout)
+        gk = self._hb_axred_kernel(nd, axes, bd.dtype, out_dtype, kind)
+        self._hb_axred_launch(gk, out_extents, red_extents,
+                              self._cont(bd).data_ptr(), off0, strides,
+                              out_t.data_ptr(), nout)
 
     def pack_temp_box(self, vname, rel_box):
         t = self.temps[vname]
@@ -1011,30 +1009,18 @@ class HipBackend:
     def tiled_kernel(self, desc):
         """Build (or fetch) the staged/tiled kernel; returns a handle token
         or None (fall back to sequential)."""
-        from . import codegen as cg
-        key = cg.staged_tiled_key(desc)
-        ck = ("tiled", key)
+        ck = ("tiled", codegen.staged_tiled_key(desc))
         cached = self.kernels.get(ck)
         if cached is None:
             try:
-                key2, source, kname, fields = cg.generate_staged_tiled(desc)
+                gk = codegen.generate_staged_tiled(desc)
             except NotImplementedError:
                 return None
-            assert key2 == key
-            if int(os.environ.get("RAMBA_SHOW_CODE", "0")):
-                print(f"=== tiled kernel {key} ===\n{source}\n", flush=True)
-            h = ctypes.c_void_p()
-            self._check(self.lib.rt_kernel_get(
-                key.encode(), source.encode(), kname.encode(),
-                ctypes.byref(h)), "rt_kernel_get(tiled)")
-            cached = (h.value, fields, key)
-            self.kernels[ck] = cached
+            assert gk.key == ck[1]
+            cached = self.kernels[ck] = self._compile(gk, "tiled")
         return cached
 
-    def tiled_launch(self, handle, vals, ntiles, red_dtypes=None,
-                     rec=None):
-        from . import codegen as cg
-        h, fields, tkkey = handle
+    def tiled_launch(self, gk, vals, ntiles, red_dtypes=None, rec=None):
         gx = max(1, min(int(os.environ.get("RAMBA_GRID_CAP", "32768")),
                         ntiles))
         red_dtypes = red_dtypes or []
@@ -1052,19 +1038,7 @@ class HipBackend:
                 vals[f"red{ri}_ptr"] = t.data_ptr()
             if rec is not None:
                 rec.partials = parts
-        args = cg.pack_tk_args(fields, vals)
-        if self.time_kernels:
-            ev0 = self.torch.cuda.Event(enable_timing=True)
-            ev1 = self.torch.cuda.Event(enable_timing=True)
-            ev0.record()
-        self._check(self.lib.rt_launch(
-            ctypes.c_void_p(h), gx, 1, 1, 256, self._stream(), args,
-            len(args)), "rt_launch(tiled)")
-        if self.time_kernels:
-            ev1.record()
-            ev1.synchronize()
-            self.kernel_times_ms.append(ev0.elapsed_time(ev1))
-            self.kernel_keys.append(tkkey)
+        self._launch(gk, (gx, 1, 1), gk.args.pack(vals), "tiled")
         out = []
         for t, dt in zip(parts, red_dtypes):
             total = self.torch.empty(1, dtype=t.dtype, device="cuda")
@@ -1082,8 +1056,7 @@ class HipBackend:
     def _maybe_load_tiled(self, plan):
         """If the plan is a qualifying 2-D stencil (>=3 same-array shifted
         readers), build the LDS load-tiled kernel instead of the vectorized
-        elementwise one.  Returns ("lt", handle, fields, fam_meta, others)
-        or None."""
+        elementwise one.  Returns its GeneratedKernel (kind 'lt') or None."""
         # measured on MI355X (profiles/README r02): at 16x256 tiles the LDS
         # kernel cuts HBM FETCH 1.56x -> 1.21-1.27x of algorithmic AND beats
         # the vectorized cross-row-sharing kernel at PRK scale (30000^2:
@@ -1096,43 +1069,29 @@ class HipBackend:
             return None
         if plan.itershape[0] * plan.itershape[1] < (1 << 16):
             return None         # rim slabs / tiny boxes: vectorized path wins
-        from . import codegen as cg
-        fams = cg.find_stencil_families(plan)
+        fams = codegen.find_stencil_families(plan)
         if not fams:
             return None
-        key, source, kname, fields, tile = cg.generate_load_tiled(plan, fams)
-        ck = ("lt", key)
-        cached = self.kernels.get(ck)
+        gk = codegen.generate_load_tiled(plan, fams)
+        cached = self.kernels.get(("lt", gk.key))
         if cached is None:
-            if int(os.environ.get("RAMBA_SHOW_CODE", "0")):
-                print(f"=== load-tiled kernel {key} ===\n{source}\n",
-                      flush=True)
-            h = ctypes.c_void_p()
-            self._check(self.lib.rt_kernel_get(
-                key.encode(), source.encode(), kname.encode(),
-                ctypes.byref(h)), "rt_kernel_get(load_tiled)")
-            cached = (h.value, fields)
-            self.kernels[ck] = cached
-        fam_meta = [(rep, anchor, s0) for (anchor, s0, dt, mem, rep) in fams]
-        member_names = {n for (a, s, dt, mem, rep) in fams
-                        for (n, _, _) in mem}
-        others = [op.name for op in plan.operands
-                  if op.name not in member_names]
-        return ("lt", cached[0], cached[1], fam_meta, others, tile, key)
+            cached = self.kernels[("lt", gk.key)] = self._compile(
+                gk, "load_tiled")
+        # fam_meta carries this plan's offsets: keep gk, share the handle
+        gk.handle = cached.handle
+        return gk
 
     def _launch_load_tiled(self, gk, plan):
-        from . import codegen as cg
-        _, handle, fields, fam_meta, others, tile, ltkey = gk
         opmap = {o.name: o for o in plan.operands}
         vals = {"n0": plan.itershape[0], "n1": plan.itershape[1],
                 "gs0": plan.global_start[0], "gs1": plan.global_start[1]}
-        for fi, (rep, anchor, s0) in enumerate(fam_meta):
+        for fi, (rep, anchor, s0) in enumerate(gk.fam_meta):
             op = opmap[rep]
             vals[f"fam{fi}_ptr"] = self._cont(op.bd).data_ptr() \
                 if op.kind == "container" else self.temps[op.name].data_ptr()
             vals[f"fam{fi}_off"] = anchor
             vals[f"fam{fi}_s0"] = s0
-        for name in others:
+        for name in gk.others:
             op = opmap[name]
             vals[f"{name}_ptr"] = self._cont(op.bd).data_ptr() \
                 if op.kind == "container" else self.temps[name].data_ptr()
@@ -1141,23 +1100,10 @@ class HipBackend:
             vals[f"{name}_s1"] = op.strides[1]
         for n, (v, dt) in plan.scalars.items():
             vals[n] = v
-        args = cg.pack_tk_args(fields, vals)
-        th, cw, seg = tile
+        th, cw, seg = gk.tile
         tiles0 = (plan.itershape[0] + th - 1) // th
         ntiles = ((tiles0 + seg - 1) // seg) \
             * ((plan.itershape[1] + cw - 1) // cw)
         gx = max(1, min(int(os.environ.get("RAMBA_GRID_CAP", "32768")),
                         ntiles))
-        if self.time_kernels:
-            ev0 = self.torch.cuda.Event(enable_timing=True)
-            ev1 = self.torch.cuda.Event(enable_timing=True)
-            ev0.record()
-        self._check(self.lib.rt_launch(
-            ctypes.c_void_p(handle), gx, 1, 1, 256, self._stream(), args,
-            len(args)), "rt_launch(load_tiled)")
-        if self.time_kernels:
-            ev1.record()
-            ev1.synchronize()
-            self.kernel_times_ms.append(ev0.elapsed_time(ev1))
-            self.kernel_keys.append(ltkey)
-        return []
+        self._launch(gk, (gx, 1, 1), gk.args.pack(vals), "load_tiled")

@@ -145,8 +145,8 @@ def test_axis_reduce_kernels_compile():
         (2, (0,), np.float64, np.bool_, "all"),
     ]
     for nd, axes, idt, odt, kind in cases:
-        key, src, kname, fields, ls = generate_axis_reduce(
-            nd, axes, np.dtype(idt), np.dtype(odt), kind)
+        src = generate_axis_reduce(
+            nd, axes, np.dtype(idt), np.dtype(odt), kind).source
         rc = lib.rt_compile_check(src.encode())
         assert rc == 0, (f"{nd}d axes={axes} {kind}: "
                          + lib.rt_last_error().decode() + "\n" + src)
@@ -155,8 +155,9 @@ def test_axis_reduce_kernels_compile():
             (2, (0,), np.float64, np.float64, "sum"),
             (2, (0,), np.int64, np.int64, "max"),
             (3, (0,), np.float32, np.float32, "sum")]:
-        key, src, kname, fields, ls = generate_axis_reduce(
-            nd, axes, np.dtype(idt), np.dtype(odt), kind, chunked=True)
+        src = generate_axis_reduce(
+            nd, axes, np.dtype(idt), np.dtype(odt), kind,
+            chunked=True).source
         rc = lib.rt_compile_check(src.encode())
         assert rc == 0, lib.rt_last_error().decode() + "\n" + src
 
