@@ -74,8 +74,8 @@ class AotCompileBackend:
             fams = codegen.find_stencil_families(plan)
             if fams:
                 self._cc(codegen.generate_load_tiled(plan, fams).source)
-        return [np.asarray(ir.reduction_init(s.kind, s.dtype),
-                           dtype=s.dtype)[()] for s in plan.reductions]
+        return [ir.reduction_identity(s.kind, s.dtype)
+                for s in plan.reductions]
 
     def axis_reduce_partial(self, bd, off0, strides, lb, axes, kind,
                             out_dtype):

@@ -31,6 +31,8 @@ argmax as to-do).
 
 import numpy as np
 
+from .shardview import box_shape, box_slices, c_strides
+
 
 def hooks_for(backend):
     """The object serving the two hooks for `backend`."""
@@ -104,14 +106,10 @@ class HostArg:
         import torch
         core = rt.core_box(bd, rt.rank)
         local = self.backend.box_to_numpy(bd, rt, core)
-        nb = local.ndim
-        dstr = [1] * nb
-        for i in range(nb - 2, -1, -1):
-            dstr[i] = dstr[i + 1] * local.shape[i + 1]
         # the operand is read in place through the view's strides
-        off0, strides = view.operand_addressing(lb[0], dstr, core[0],
-                                                (0,) * nb)
-        shape = tuple(int(s) for s in (lb[1] - lb[0] + 1))
+        off0, strides = view.operand_addressing(
+            lb[0], c_strides(local.shape), core[0], (0,) * local.ndim)
+        shape = box_shape(lb)
         flat = local.reshape(-1)
         x = np.lib.stride_tricks.as_strided(
             flat[off0:] if off0 else flat, shape=shape,
@@ -132,12 +130,8 @@ class HostArg:
                         kind, skipna):
         core = rt.core_box(out_bd, rt.rank)
         cur = self.backend.box_to_numpy(out_bd, rt, core).copy()
-        sl_i = tuple(slice(int(box[0, i] - core[0, i]),
-                           int(box[1, i] - core[0, i]) + 1)
-                     for i in range(cur.ndim))
-        sl_v = tuple(slice(int(rel[0, i]), int(rel[1, i]) + 1)
-                     for i in range(cur.ndim))
-        bv = best.numpy()[sl_v]          # shares memory with `best`
+        sl_i = box_slices(box, core[0])
+        bv = best.numpy()[box_slices(rel)]   # shares memory with `best`
         sv = src_vals.numpy().reshape(bv.shape)
         si = src_idx.numpy().reshape(bv.shape)
         take = better(sv, si, bv, cur[sl_i], kind, skipna)

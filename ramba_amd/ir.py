@@ -168,6 +168,12 @@ def reduction_init(kind, dtype):
     return init
 
 
+def reduction_identity(kind, dtype):
+    """reduction_init as a 0-d value of `dtype`: the partial of a rank (or
+    box) that holds nothing."""
+    return np.asarray(reduction_init(kind, dtype), dtype=dtype)[()]
+
+
 # ---------------------------------------------------------------------------
 # statements
 # ---------------------------------------------------------------------------

@@ -12,8 +12,9 @@ import numbers
 import numpy as np
 
 from . import deferred, ir
-from .common import default_border, default_divisions
-from .shardview import View
+from .common import (contiguous_divisions, default_border,
+                     default_divisions)
+from .shardview import View, exec_boxes, spans_trailing_axes
 
 
 # ---------------------------------------------------------------------------
@@ -174,7 +175,6 @@ class ndarray:
             # partition through the fused engine: cross-rank C-order
             # concatenation of per-rank compactions is then always valid,
             # whatever the source partitions look like
-            from .common import contiguous_divisions
             rt = deferred.get_runtime()
             cdivs = contiguous_divisions(rt.world, self.shape)
             ta_bd = deferred.bdarray(self.shape, self.dtype, cdivs,
@@ -819,7 +819,6 @@ def _index_to_i64(arr, rt):
     """The index as a constructed 1-D int64 ramba array of length arr.size
     on contiguous_divisions (N-D indices ravelled); other integer dtypes are
     cast through the fused engine, host data comes in by scatter."""
-    from .common import contiguous_divisions
     m = int(arr.size)
     cdivs = contiguous_divisions(rt.world, (m,))
     bd = deferred.bdarray((m,), np.dtype(np.int64), cdivs, default_border,
@@ -852,18 +851,10 @@ def _take_source(src, rt):
     contiguous_divisions through the fused engine."""
     bd = src.bdarray
     if bd.constructed and src.view.is_identity_for(bd.shape):
-        ok = True
-        for r in range(rt.world):
-            cb = rt.core_box(bd, r)
-            if cb is None:
-                continue
-            for dax in range(1, len(bd.shape)):
-                if not (cb[0, dax] == 0
-                        and cb[1, dax] == bd.shape[dax] - 1):
-                    ok = False
-        if ok:
+        cores = [rt.core_box(bd, r) for r in range(rt.world)]
+        if all(cb is None or spans_trailing_axes(cb, bd.shape)
+               for cb in cores):
             return src
-    from .common import contiguous_divisions
     t_bd = deferred.bdarray(src.shape, src.dtype,
                             contiguous_divisions(rt.world, src.shape),
                             default_border, flex=False)
@@ -1629,12 +1620,9 @@ def _nd_reshape(self, *newshape):
     # interval exchange needs C-contiguous source shards; repartition
     # through the fused engine (a plain assignment onto an array with
     # prescribed axis-0 divisions) when the schedule split trailing axes
-    from .runtime import _flat_interval
-    from .shardview import exec_boxes as _eb
-    lbs = _eb(src.view, src.bdarray.divisions)
-    if any(b is not None and _flat_interval(b, src.view.shape) is None
+    lbs = exec_boxes(src.view, src.bdarray.divisions)
+    if any(b is not None and not spans_trailing_axes(b, src.view.shape)
            for b in lbs):
-        from .common import contiguous_divisions
         tmp_bd = deferred.bdarray(
             self.shape, self.dtype,
             contiguous_divisions(rt.world, self.shape),

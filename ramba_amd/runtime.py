@@ -17,15 +17,17 @@ container that covers its division box plus a border ring
    gather-to-driver, ramba.py:5745-5764/5852-5863).
 """
 
-import os
 import time
 
 import numpy as np
 
 from . import common, deferred, ir
-from .common import add_time, default_border, default_divisions
-from .shardview import (box_contains, box_intersect, box_shape,
-                        box_subtract)
+from .common import (add_time, contiguous_divisions, default_border,
+                     default_divisions)
+from .shardview import (box_contains, box_intersect, box_rel, box_shape,
+                        box_slices, box_subtract, c_strides, coord_offset,
+                        divisions_from_boxes, exec_boxes,
+                        spans_trailing_axes)
 
 
 class OperandPlan:
@@ -136,10 +138,21 @@ class Runtime:
                 sz = -(-sz // align) * align + align
             cshape.append(sz)
         cshape = tuple(cshape)
-        cstrides = [1] * nd
-        for i in range(nd - 2, -1, -1):
-            cstrides[i] = cstrides[i + 1] * cshape[i + 1]
-        return d, cshape, tuple(cstrides), pads
+        return d, cshape, c_strides(cshape), pads
+
+    def local_addressing(self, bd, view, lb):
+        """(offset0, strides) addressing view box `lb` of `bd` in this
+        rank's container."""
+        d, _, cstrides, pads = self.shard_geometry(bd)
+        return view.operand_addressing(lb[0], cstrides, d[0], pads)
+
+    def new_result(self, shape, dtype, divisions):
+        """A fresh array on `divisions`, allocated on every rank."""
+        bd = deferred.bdarray(shape, dtype, divisions, default_border,
+                              flex=False)
+        self.backend.alloc_container(bd, self)
+        bd.constructed = True
+        return bd
 
     def core_box(self, bd, r):
         d = bd.divisions[r]
@@ -206,13 +219,22 @@ class Runtime:
         finally:
             add_time("run_deferred_ops", time.perf_counter() - t0)
 
-    def _execute_group(self, group):
-        ntiming = common.ntiming
-        t0 = time.perf_counter() if ntiming else 0.0
-        live, dead = deferred.compute_live_vars(group)
-        cache = getattr(self, "_recipe_cache", None)
+    def _recipes(self):
+        """The recipe cache, created on first use."""
+        cache = self.__dict__.get("_recipe_cache")
         if cache is None:
             cache = self._recipe_cache = {}
+        return cache
+
+    def _execute_group(self, group, live=None, dead=None, record_pure=True):
+        """Plan the group (or find its cached plan) and run it.  `live,
+        dead` override the liveness split: the recipe is keyed on the split
+        it was planned for."""
+        ntiming = common.ntiming
+        t0 = time.perf_counter() if ntiming else 0.0
+        if live is None:
+            live, dead = deferred.compute_live_vars(group)
+        cache = self._recipes()
         try:
             sig = self._group_signature(group, live)
         except TypeError:
@@ -220,16 +242,17 @@ class Runtime:
         if ntiming:
             add_time("eg_signature", time.perf_counter() - t0)
         recipe = cache.get(sig) if sig is not None else None
-        if recipe is not None:
-            self._run_recipe(recipe, group, live)
-            self._record_pure(recipe, group, live)
-            return
-        recipe = self._build_and_run(group, live, dead)
-        self._record_pure(recipe, group, live)
-        if sig is not None and recipe is not None:
+        planned = recipe is None
+        if planned:
+            recipe = self._plan_group(group, live, dead)
+        self._run_recipe(recipe, group, live)
+        if planned and sig is not None:
+            # stored only once it ran: a group that fails is planned again
             if len(cache) > 128:
                 cache.clear()
             cache[sig] = recipe
+        if record_pure:
+            self._record_pure(recipe, group, live)
 
     def _record_pure(self, recipe, group, live):
         """Provenance for rematerialisation (common.remat): store a recipe
@@ -245,18 +268,36 @@ class Runtime:
         if targets:
             deferred.record_pure(group, live, targets)
 
+    def adopt_and_alloc(self, group, live, adopted=None, alloc=True):
+        """Flex arrays of the group's shape adopt its partition
+        (ramba.py:8093-8101) -- `adopted` when a recipe already holds the
+        divisions, else the group's exec boxes -- and every live array is
+        allocated on first use (ramba.py:3506).  Returns the adopted
+        divisions (None: no array was flex)."""
+        for oi in live.values():
+            bd = oi.bd
+            if bd.is_flex and bd.shape == group.shape:
+                if adopted is None:
+                    adopted = divisions_from_boxes(group.exec_boxes(),
+                                                   len(group.shape))
+                bd.divisions = adopted
+                bd.flex = False
+            if alloc and not bd.constructed:
+                self.backend.alloc_container(bd, self)
+                bd.constructed = True
+        return adopted
+
+    def free_shards(self, bds):
+        for bd in bds:
+            if bd.constructed:
+                self.backend.free_container(bd)
+                bd.constructed = False
+
     def _run_recipe(self, recipe, group, live):
-        """Re-run a cached recipe against the current group's backing
-        arrays (pointers differ; geometry is identical by signature)."""
-        # flex adoption + allocation
-        for name, oi in live.items():
-            if oi.bd.is_flex and oi.bd.shape == group.shape \
-                    and recipe.adopted_divs is not None:
-                oi.bd.divisions = recipe.adopted_divs
-                oi.bd.flex = False
-            if not oi.bd.constructed:
-                self.backend.alloc_container(oi.bd, self)
-                oi.bd.constructed = True
+        """Run a planned recipe against the group's backing arrays: on the
+        step that planned it and, from the cache, on every later step
+        (pointers differ; geometry is identical by signature)."""
+        self.adopt_and_alloc(group, live, recipe.adopted_divs)
         # rebind operand backing arrays
         plan = recipe.plan
         plan.scalars = dict(group.scalars)
@@ -301,44 +342,25 @@ class Runtime:
             if plan.itershape is not None:
                 partials = self.backend.launch(plan, recipe)
             else:
-                partials = [np.asarray(
-                    ir.reduction_init(spec.kind, spec.dtype),
-                    dtype=spec.dtype)[()] for spec in plan.reductions]
+                # empty exec box: this rank contributes the identities
+                partials = [ir.reduction_identity(spec.kind, spec.dtype)
+                            for spec in plan.reductions]
             if ntiming:
                 add_time("eg_launch_host", time.perf_counter() - tl)
         for (spec, pend), val in zip(group.reductions, partials):
             pend.partial = np.asarray(val, dtype=spec.dtype)[()]
         self.backend.free_temps()
-        for bd in group.delete_bds:
-            if bd.constructed:
-                self.backend.free_container(bd)
-                bd.constructed = False
+        # deferred frees (ramba.py:8321-8328)
+        self.free_shards(group.delete_bds)
 
-    def _build_and_run(self, group, live, dead):
+    def _plan_group(self, group, live, dead):
+        """The Recipe of a fused group: which boxes move between ranks,
+        which temps hold operands that fit no border, and the launch(es)
+        with their operand addressing.  Pure geometry: no backend call, and
+        the only state touched is the flex adoption the box math needs."""
         eboxes = group.exec_boxes()
         recipe = Recipe()
-
-        # flex arrays adopt the group's partition (ramba.py:8093-8101)
-        nd = len(group.shape)
-        adopted = None
-        for oi in live.values():
-            if oi.bd.is_flex and oi.bd.shape == group.shape:
-                if adopted is None:
-                    adopted = np.zeros((self.world, 2, nd), dtype=np.int64)
-                    for r, b in enumerate(eboxes):
-                        if b is None:
-                            adopted[r, 1, :] = -1
-                        else:
-                            adopted[r] = b
-                oi.bd.divisions = adopted
-                oi.bd.flex = False
-        recipe.adopted_divs = adopted
-
-        # allocate + mark constructed (creation on first use, ramba.py:3506)
-        for oi in live.values():
-            if not oi.bd.constructed:
-                self.backend.alloc_container(oi.bd, self)
-                oi.bd.constructed = True
+        recipe.adopted_divs = self.adopt_and_alloc(group, live, alloc=False)
 
         plan = KernelPlan()
         plan.scalars = dict(group.scalars)
@@ -408,78 +430,36 @@ class Runtime:
             if r == self.rank:
                 my_plans = per_gid
 
-        # ---- allocate temp operand buffers + copy local parts
+        # ---- temp operand buffers: the need box, and the part of it this
+        # rank owns (copied locally; the rest arrives as "temp" messages)
         temp_geom = {}   # var -> (need box, strides)
         for gid, (bd, owner, fill, temp_vars) in my_plans.items():
+            core = self.core_box(bd, self.rank)
             for vname, need in temp_vars.items():
                 shape = box_shape(need)
-                self.backend.alloc_temp(vname, shape, bd.dtype)
-                strides = [1] * len(shape)
-                for i in range(len(shape) - 2, -1, -1):
-                    strides[i] = strides[i + 1] * shape[i + 1]
-                temp_geom[vname] = (need, tuple(strides))
-                core = self.core_box(bd, self.rank)
-                part = box_intersect(need, core)
+                temp_geom[vname] = (need, c_strides(shape))
                 recipe.temp_specs.append(
-                    (vname, shape, bd.dtype, owner, need, part))
-                if part is not None and bd.constructed:
-                    self.backend.copy_container_to_temp(bd, self, part,
-                                                        vname, need)
+                    (vname, shape, bd.dtype, owner, need,
+                     box_intersect(need, core)))
         recipe.temp_geom = temp_geom
         recipe.comm_msgs = comm_msgs
 
-        # ---- launches, with the exchange posted first and (when the
-        # geometry allows) the interior launched while it is in flight
+        # ---- launches: split into units when the geometry lets the
+        # interior run while the exchange is in flight, else one launch
+        # over the rank's box (itershape None: the box is empty)
         ib = eboxes[self.rank]
-        split_boxes, pre_wait = self._plan_overlap_split(
+        split_boxes, recipe.pre_wait_units = self._plan_overlap_split(
             ib, comm_msgs, plan, temp_geom, live)
-        state = None
-        if comm_msgs:
-            msgs = [(dst, src, live[owner].bd, bx, tgt)
-                    for (dst, src, owner, bx, tgt) in comm_msgs]
-            state = self._comms_begin(msgs, temp_geom)
         if split_boxes is not None:
             recipe.units = [
                 LaunchUnit(self._address_plan(plan, live, b, temp_geom))
                 for b in split_boxes]
-            recipe.pre_wait_units = pre_wait
-            plan.itershape = None
-            for i, u in enumerate(recipe.units):
-                if i == pre_wait and state is not None:
-                    self._comms_finish(state)
-                    state = None
-                self.backend.launch(u.plan, u)
-            if state is not None:
-                self._comms_finish(state)
-                state = None
-            partials = []
-        else:
-            if state is not None:
-                self._comms_finish(state)
-                state = None
-            if ib is not None:
-                ap = self._address_plan(plan, live, ib, temp_geom)
-                plan.itershape = ap.itershape
-                plan.global_start = ap.global_start
-                plan.operands = ap.operands
-                partials = self.backend.launch(plan, recipe)
-            else:
-                plan.itershape = None
-                partials = [np.asarray(
-                    ir.reduction_init(spec.kind, spec.dtype),
-                    dtype=spec.dtype)[()] for spec in plan.reductions]
+        elif ib is not None:
+            ap = self._address_plan(plan, live, ib, temp_geom)
+            plan.itershape = ap.itershape
+            plan.global_start = ap.global_start
+            plan.operands = ap.operands
         recipe.plan = plan
-
-        for (spec, pend), val in zip(group.reductions, partials):
-            pend.partial = np.asarray(val, dtype=spec.dtype)[()]
-
-        self.backend.free_temps()
-
-        # ---- deferred frees (ramba.py:8321-8328)
-        for bd in group.delete_bds:
-            if bd.constructed:
-                self.backend.free_container(bd)
-                bd.constructed = False
         return recipe
 
     # ------------------------------------------------------------------
@@ -525,8 +505,7 @@ class Runtime:
         that only SENDS launches its whole box early.  Groups with
         reductions or temp-materialised operands stay sequential (the
         reference's serial order, ramba.py:3547-3693, is the fallback)."""
-        from .common import overlap_exchange
-        if (not overlap_exchange or ib is None or not comm_msgs
+        if (not common.overlap_exchange or ib is None or not comm_msgs
                 or plan.reductions or temp_geom):
             return None, 0
         if not any(dst == self.rank for (dst, _, _, _, _) in comm_msgs):
@@ -590,9 +569,6 @@ class Runtime:
                 self.backend.unpack_box_to_temp(vname, need, bx, buf)
         add_time("part_exchange", time.perf_counter() - tc0)
 
-    def _do_comms(self, msgs, temp_geom):
-        self._comms_finish(self._comms_begin(msgs, temp_geom))
-
     # ------------------------------------------------------------------
     # cross-stage fusion (BASELINE configs[4]): a sealed producer group
     # (index-pure elementwise, identity writes) + its consumer group
@@ -621,33 +597,15 @@ class Runtime:
         keep = [bd for bd in g1.delete_bds if bd.gid in extra]
         g1.delete_bds = [bd for bd in g1.delete_bds if bd.gid not in extra]
         g2.delete_bds.extend(keep)
-        self._execute_group_with(g1, live, dead)
+        # the sealed producer runs late, after its consumer's writes were
+        # registered: it records no provenance (see _record_pure)
+        self._execute_group(g1, live, dead, record_pure=False)
         self._execute_group(g2)
         if g2.staged_reductions:
             # the reduction that was fused onto the pair: the sequential
             # order recomputes it over the full local core
             from . import staged_exec
             staged_exec.finish_staged_reductions(self, g2)
-
-    def _execute_group_with(self, group, live, dead):
-        """_execute_group with a precomputed liveness split (recipe cache
-        keyed on the extra-live-adjusted liveness)."""
-        cache = getattr(self, "_recipe_cache", None)
-        if cache is None:
-            cache = self._recipe_cache = {}
-        try:
-            sig = self._group_signature(group, live)
-        except TypeError:
-            sig = None
-        recipe = cache.get(sig) if sig is not None else None
-        if recipe is not None:
-            self._run_recipe(recipe, group, live)
-            return
-        recipe = self._build_and_run(group, live, dead)
-        if sig is not None and recipe is not None:
-            if len(cache) > 128:
-                cache.clear()
-            cache[sig] = recipe
 
     def _try_execute_tiled(self, g1, g2):
         """Fused LDS-tiled execution of the pair; False -> caller falls
@@ -679,24 +637,16 @@ class Runtime:
             else:
                 part = None
             part = self.backend.bcast_numpy(part, root=r)
-            sl = tuple(slice(int(core[0, i]), int(core[1, i]) + 1)
-                       for i in range(len(bd.shape)))
-            base[sl] = part
+            base[box_slices(core)] = part
         return numpy_view(base, view)
 
     def container_slice(self, bd, box, r=None):
         """Container index slices covering a global base box."""
         d = bd.divisions[self.rank if r is None else r]
-        nd = len(bd.shape)
-        pads = self.lo_pads(bd)
-        return tuple(slice(int(box[0, i] - d[0, i]) + pads[i],
-                           int(box[1, i] - d[0, i]) + pads[i] + 1)
-                     for i in range(nd))
+        return box_slices(box, d[0] - np.asarray(self.lo_pads(bd)))
 
     def free_shard(self, bd):
-        if bd.constructed:
-            self.backend.free_container(bd)
-            bd.constructed = False
+        self.free_shards((bd,))
 
     def scatter_numpy(self, bd, nparr):
         """Distribute a host array: each rank copies its core slice."""
@@ -708,10 +658,9 @@ class Runtime:
         bd.pure = None      # host data overwrites any index-pure content
         core = self.core_box(bd, self.rank)
         if core is not None:
-            sl = tuple(slice(int(core[0, i]), int(core[1, i]) + 1)
-                       for i in range(len(bd.shape)))
             self.backend.write_core_from_numpy(
-                bd, self, np.ascontiguousarray(nparr[sl], dtype=bd.dtype))
+                bd, self, np.ascontiguousarray(nparr[box_slices(core)],
+                                               dtype=bd.dtype))
 
     def read_element(self, bd, coords):
         box = np.array([coords, coords], dtype=np.int64)
@@ -763,64 +712,67 @@ def _proj_box(box, axes):
     return out
 
 
+def _msg_key(m):
+    """Sort key of a (dst, src, box) message: the same order on every rank."""
+    return (m[0], m[1], tuple(m[2][0]), tuple(m[2][1]))
+
+
+def combine_plan(self, lbs, axes, out_bd):
+    """The combining exchange of a reduction over `axes`, identical on every
+    rank: each rank's exec box, projected, goes to the owners of the result
+    cells it covers.  Sorted list of (dst, src, keepdims-space box)."""
+    msgs = []
+    for r, lb in enumerate(lbs):
+        if lb is None:
+            continue
+        pb = _proj_box(lb, axes)
+        for s in range(self.world):
+            part = box_intersect(pb, self.core_box(out_bd, s))
+            if part is not None:
+                msgs.append((s, r, part))
+    msgs.sort(key=_msg_key)
+    return msgs
+
+
+Runtime.combine_plan = combine_plan
+
+
 def reduce_axes_op(self, arr, axes, kind, out_dtype, kd_shape):
     """Distributed axis reduction: local strided-reduce kernel into a
     per-rank partial, then cross-rank combining box exchange into a fresh
     result array (replaces the reference's axis_reduce loops 8231-8244 +
     internal_reduction2 slice combine 5818-5849)."""
-    from .shardview import exec_boxes as _eb
     bd, v = arr.bdarray, arr.view
     axes = tuple(sorted(axes))
-    out_bd = deferred.bdarray(kd_shape, out_dtype,
-                              default_divisions(self.world, kd_shape),
-                              default_border, flex=False)
-    self.backend.alloc_container(out_bd, self)
-    out_bd.constructed = True
+    out_bd = self.new_result(kd_shape, out_dtype,
+                             default_divisions(self.world, kd_shape))
     ident = ir.reduction_init(kind, out_dtype)
     self.backend.fill_container(out_bd, self, ident)
 
-    lbs = _eb(v, bd.divisions)
+    lbs = exec_boxes(v, bd.divisions)
     lb = lbs[self.rank]
     if lb is not None:
-        d_, cshape, cstrides, pads = self.shard_geometry(bd)
-        off0, strides = v.operand_addressing(lb[0], cstrides, d_[0], pads)
+        off0, strides = self.local_addressing(bd, v, lb)
         self.backend.axis_reduce_partial(
             bd, off0, strides, lb, axes, kind, out_dtype)
 
-    # combining exchange plan (deterministic on every rank)
-    msgs = []
-    for r in range(self.world):
-        if lbs[r] is None:
-            continue
-        pb = _proj_box(lbs[r], axes)
-        for s in range(self.world):
-            part = box_intersect(pb, self.core_box(out_bd, s))
-            if part is not None:
-                msgs.append((s, r, part))
-    msgs.sort(key=lambda m: (m[0], m[1], tuple(m[2][0]), tuple(m[2][1])))
-
     my_pb = _proj_box(lb, axes) if lb is not None else None
     sends, recvs, locals_ = [], [], []
-    for (dst, src, bx) in msgs:
+    for (dst, src, bx) in self.combine_plan(lbs, axes, out_bd):
         if src == self.rank and dst == self.rank:
             locals_.append(bx)
             continue
         if src == self.rank:
-            rel = bx.copy()
-            rel[0] -= my_pb[0]
-            rel[1] -= my_pb[0]
-            sends.append((dst, self.backend.pack_temp_box("__axred__", rel)))
+            sends.append((dst, self.backend.pack_temp_box(
+                "__axred__", box_rel(bx, my_pb[0]))))
         if dst == self.rank:
             buf = self.backend.new_message_buffer(box_shape(bx), out_dtype)
             recvs.append((src, buf, bx))
     if sends or recvs:
         self.backend.exchange(sends, [(s, b) for (s, b, _) in recvs])
     for bx in locals_:
-        rel = bx.copy()
-        rel[0] -= my_pb[0]
-        rel[1] -= my_pb[0]
-        self.backend.combine_temp_into_container(out_bd, self, bx,
-                                                 "__axred__", rel, kind)
+        self.backend.combine_temp_into_container(
+            out_bd, self, bx, "__axred__", box_rel(bx, my_pb[0]), kind)
     for (src, buf, bx) in recvs:
         self.backend.combine_box_into_container(out_bd, self, bx, buf, kind)
     self.backend.free_temps()
@@ -837,31 +789,18 @@ Runtime.reduce_axes_op = reduce_axes_op
 # ---------------------------------------------------------------------------
 
 def cumsum_op(self, arr, out_dtype):
-    from .shardview import exec_boxes as _eb
     bd, v = arr.bdarray, arr.view
     assert v.ndim == 1, "cumsum is 1-D (reference scumulative)"
-    lbs = _eb(v, bd.divisions)
+    lbs = exec_boxes(v, bd.divisions)
     # result partitioned by the input's exec boxes (no data exchange)
-    nd = 1
-    divs = np.zeros((self.world, 2, nd), dtype=np.int64)
-    starts = []
-    for r, b in enumerate(lbs):
-        if b is None:
-            divs[r, 1, :] = -1
-            starts.append(None)
-        else:
-            divs[r] = b
-            starts.append(int(b[0, 0]))
-    out_bd = deferred.bdarray(v.shape, out_dtype, divs, default_border,
-                              flex=False)
-    self.backend.alloc_container(out_bd, self)
-    out_bd.constructed = True
+    starts = [None if b is None else int(b[0, 0]) for b in lbs]
+    out_bd = self.new_result(v.shape, out_dtype,
+                             divisions_from_boxes(lbs, 1))
 
     lb = lbs[self.rank]
     local_total = np.asarray(0, dtype=out_dtype)[()]
     if lb is not None:
-        d_, cshape, cstrides, pads = self.shard_geometry(bd)
-        off0, strides = v.operand_addressing(lb[0], cstrides, d_[0], pads)
+        off0, strides = self.local_addressing(bd, v, lb)
         n_local = int(lb[1, 0] - lb[0, 0] + 1)
         local_total = self.backend.cumsum_local_phase12(
             bd, off0, strides[0], n_local, out_dtype)
@@ -874,8 +813,8 @@ def cumsum_op(self, arr, out_dtype):
             if starts[r] is not None and starts[r] < my_start:
                 offset = np.asarray(offset + totals[r], dtype=out_dtype)[()]
     if lb is not None:
-        dd, _, ocs, opads = self.shard_geometry(out_bd)
-        out_off = opads[0]
+        od, _, ocs, opads = self.shard_geometry(out_bd)
+        out_off = coord_offset(lb[0], od[0], opads, ocs)
         self.backend.cumsum_local_phase3(bd, off0, strides[0], n_local,
                                          out_bd, out_off, offset, out_dtype)
     self.backend.free_temps()
@@ -903,14 +842,12 @@ def mask_compact_op(self, bd_a, bd_m):
         cb = self.core_box(bd_a, r)
         if cb is None:
             continue
-        # C-order concatenation across ranks needs each rank's box to
-        # span the full extent of every axis but the first
-        for dax in range(1, nd):
-            if not (cb[0, dax] == 0
-                    and cb[1, dax] == bd_a.shape[dax] - 1):
-                raise NotImplementedError(
-                    "a[mask] needs C-contiguous (axis-0 split) partitions "
-                    f"for nd>={nd}; got division {cb.tolist()} of rank {r}")
+        # C-order concatenation across ranks needs each rank's box to be
+        # one C-order interval
+        if not spans_trailing_axes(cb, bd_a.shape):
+            raise NotImplementedError(
+                "a[mask] needs C-contiguous (axis-0 split) partitions "
+                f"for nd>={nd}; got division {cb.tolist()} of rank {r}")
         order.append((int(cb[0, 0]), r))
     order.sort()
 
@@ -921,18 +858,11 @@ def mask_compact_op(self, bd_a, bd_m):
         prefix[r] = run
         run += int(counts[r])
     total = run
-    divs = np.zeros((self.world, 2, 1), dtype=np.int64)
-    for r in range(self.world):
-        c = int(counts[r])
-        if c == 0:
-            divs[r, 1, 0] = -1
-        else:
-            divs[r, 0, 0] = prefix[r]
-            divs[r, 1, 0] = prefix[r] + c - 1
-    out_bd = deferred.bdarray((total,), bd_a.dtype, divs, default_border,
-                              flex=False)
-    self.backend.alloc_container(out_bd, self)
-    out_bd.constructed = True
+    boxes = [None if int(counts[r]) == 0 else
+             np.array([[prefix[r]], [prefix[r] + int(counts[r]) - 1]])
+             for r in range(self.world)]
+    out_bd = self.new_result((total,), bd_a.dtype,
+                             divisions_from_boxes(boxes, 1))
     if count:
         self.backend.write_local_dense(out_bd, self, local)
     self.backend.free_temps()
@@ -953,30 +883,19 @@ Runtime.mask_compact_op = mask_compact_op
 # ---------------------------------------------------------------------------
 
 def cumsum_axis_op(self, arr, axis, out_dtype):
-    from .shardview import exec_boxes as _eb
     bd, v = arr.bdarray, arr.view
     nd = v.ndim
     assert 0 <= axis < nd and nd >= 2
     assert np.dtype(bd.dtype) == np.dtype(out_dtype)  # frontend casts
-    lbs = _eb(v, bd.divisions)
-    divs = np.zeros((self.world, 2, nd), dtype=np.int64)
-    for r, b in enumerate(lbs):
-        if b is None:
-            divs[r, 1, :] = -1
-        else:
-            divs[r] = b
-    out_bd = deferred.bdarray(v.shape, out_dtype, divs, default_border,
-                              flex=False)
-    self.backend.alloc_container(out_bd, self)
-    out_bd.constructed = True
+    lbs = exec_boxes(v, bd.divisions)
+    out_bd = self.new_result(v.shape, out_dtype,
+                             divisions_from_boxes(lbs, nd))
 
     lb = lbs[self.rank]
     if lb is not None:
-        d_, _, cstrides, pads = self.shard_geometry(bd)
-        off0, strides = v.operand_addressing(lb[0], cstrides, d_[0], pads)
+        off0, strides = self.local_addressing(bd, v, lb)
         od, _, ocs, opads = self.shard_geometry(out_bd)
-        out_off = sum((int(lb[0, i]) - int(od[0, i]) + opads[i]) * ocs[i]
-                      for i in range(nd))
+        out_off = coord_offset(lb[0], od[0], opads, ocs)
         self.backend.axis_scan_local(bd, off0, strides, box_shape(lb),
                                      axis, out_bd, out_off, ocs)
 
@@ -999,17 +918,14 @@ def cumsum_axis_op(self, arr, axis, out_dtype):
                 inter = box_intersect(_proj(br), _proj(bs))
                 if inter is not None:
                     msgs.append((s_, r_, inter))
-    msgs.sort(key=lambda m: (m[0], m[1], tuple(m[2][0]), tuple(m[2][1])))
+    msgs.sort(key=_msg_key)
 
     my_lines = _proj(lb) if lb is not None else None
     sends, recvs = [], []
     for (dst, src, bx) in msgs:
         if src == self.rank:
-            rel = bx.copy()
-            rel[0] -= my_lines[0]
-            rel[1] -= my_lines[0]
-            sends.append((dst,
-                          self.backend.pack_temp_box("__axcs_tot__", rel)))
+            sends.append((dst, self.backend.pack_temp_box(
+                "__axcs_tot__", box_rel(bx, my_lines[0]))))
         if dst == self.rank:
             recvs.append((src,
                           self.backend.new_message_buffer(box_shape(bx),
@@ -1019,10 +935,7 @@ def cumsum_axis_op(self, arr, axis, out_dtype):
     if sends or recvs:
         self.backend.exchange(sends, [(s, b) for (s, b, _) in recvs])
     for (src, buf, bx) in recvs:
-        rel = bx.copy()
-        rel[0] -= my_lines[0]
-        rel[1] -= my_lines[0]
-        self.backend.axcs_accumulate(rel, buf)
+        self.backend.axcs_accumulate(box_rel(bx, my_lines[0]), buf)
     if recvs:
         self.backend.axcs_apply(out_bd, self, lb, axis)
     self.backend.free_temps()
@@ -1044,19 +957,16 @@ Runtime.cumsum_axis_op = cumsum_axis_op
 def _flat_interval(box, shape):
     """(lo, hi_exclusive) flat C-order range of `box` if it is contiguous
     (spans full extent on every axis but the first), else None."""
-    nd = len(shape)
-    for d in range(1, nd):
-        if not (int(box[0, d]) == 0 and int(box[1, d]) == shape[d] - 1):
-            return None
+    if not spans_trailing_axes(box, shape):
+        return None
     inner = 1
-    for d in range(1, nd):
+    for d in range(1, len(shape)):
         inner *= shape[d]
     return int(box[0, 0]) * inner, (int(box[1, 0]) + 1) * inner
 
 
 def reshape_op(self, arr, newshape):
     bd, v = arr.bdarray, arr.view
-    from .shardview import exec_boxes as _eb
     newshape = tuple(int(x) for x in newshape)
     total = 1
     for x in v.shape:
@@ -1066,16 +976,12 @@ def reshape_op(self, arr, newshape):
         ntotal *= x
     assert total == ntotal, f"cannot reshape {v.shape} into {newshape}"
 
-    from .common import contiguous_divisions
-    out_bd = deferred.bdarray(newshape, bd.dtype,
-                              contiguous_divisions(self.world, newshape),
-                              default_border, flex=False)
-    self.backend.alloc_container(out_bd, self)
-    out_bd.constructed = True
+    out_bd = self.new_result(newshape, bd.dtype,
+                             contiguous_divisions(self.world, newshape))
     if total == 0:
         return out_bd
 
-    lbs = _eb(v, bd.divisions)
+    lbs = exec_boxes(v, bd.divisions)
     src_iv, dst_iv = [], []
     for r in range(self.world):
         b = lbs[r]
@@ -1108,13 +1014,12 @@ def reshape_op(self, arr, newshape):
 
     lb = lbs[self.rank]
     if lb is not None:
-        d_, _, cstrides, pads = self.shard_geometry(bd)
-        off0, strides = v.operand_addressing(lb[0], cstrides, d_[0], pads)
+        off0, strides = self.local_addressing(bd, v, lb)
         src_shape = box_shape(lb)
     ob = self.core_box(out_bd, self.rank)
     if ob is not None:
         _, _, ocs, opads = self.shard_geometry(out_bd)
-        out_off = sum(opads[i] * ocs[i] for i in range(len(newshape)))
+        out_off = coord_offset(ob[0], ob[0], opads, ocs)
         dst_shape = box_shape(ob)
 
     cont_in = self.backend._cont(bd) if lb is not None else None
@@ -1164,7 +1069,6 @@ Runtime.reshape_op = reshape_op
 
 def take_op(self, src_bd, idx_bd):
     from . import rowgather as _take
-    from .common import contiguous_divisions
     assert len(idx_bd.shape) == 1 and idx_bd.dtype == np.int64
     nrows, row_shape = src_bd.shape[0], tuple(src_bd.shape[1:])
     m = idx_bd.shape[0]
@@ -1173,19 +1077,15 @@ def take_op(self, src_bd, idx_bd):
         cb = self.core_box(src_bd, r)
         if cb is None:
             continue
-        for dax in range(1, len(src_bd.shape)):
-            assert cb[0, dax] == 0 and cb[1, dax] == src_bd.shape[dax] - 1, \
-                "take_op: source shards must span axes 1.. (frontend " \
-                "repartitions first)"
+        assert spans_trailing_axes(cb, src_bd.shape), \
+            "take_op: source shards must span axes 1.. (frontend " \
+            "repartitions first)"
         owners.append((int(cb[0, 0]), r))
     owners.sort()
 
     out_shape = (m,) + row_shape
-    out_bd = deferred.bdarray(out_shape, src_bd.dtype,
-                              contiguous_divisions(self.world, out_shape),
-                              default_border, flex=False)
-    self.backend.alloc_container(out_bd, self)
-    out_bd.constructed = True
+    out_bd = self.new_result(out_shape, src_bd.dtype,
+                             contiguous_divisions(self.world, out_shape))
     assert np.array_equal(out_bd.divisions[:, :, 0], idx_bd.divisions[:, :, 0])
 
     hooks = _take.hooks_for(self.backend)
@@ -1248,20 +1148,16 @@ def arg_reduce_op(self, arr, axis, kind, skipna):
     """axis None: the global C-order flat index as an int (-1: skipna and
     everything is NaN).  Otherwise the int64 keepdims result's bdarray,
     holding -1 where skipna met an all-NaN line."""
-    from .shardview import exec_boxes as _eb
     from . import argreduce as _ar
     bd, v = arr.bdarray, arr.view
     nd = v.ndim
     hooks = _ar.hooks_for(self.backend)
     if axis is None:
-        mult = [1] * nd
-        for d in range(nd - 2, -1, -1):
-            mult[d] = mult[d + 1] * v.shape[d + 1]
-        mult = tuple(mult)
+        mult = c_strides(v.shape)
     else:
         mult = tuple(1 if d == axis else 0 for d in range(nd))
 
-    lbs = _eb(v, bd.divisions)
+    lbs = exec_boxes(v, bd.divisions)
     lb = lbs[self.rank]
     vals = idxs = None
     if lb is not None:
@@ -1289,11 +1185,8 @@ def arg_reduce_op(self, arr, axis, kind, skipna):
 
     kd_shape = tuple(1 if d == axis else v.shape[d] for d in range(nd))
     out_dtype = np.dtype(np.int64)
-    out_bd = deferred.bdarray(kd_shape, out_dtype,
-                              default_divisions(self.world, kd_shape),
-                              default_border, flex=False)
-    self.backend.alloc_container(out_bd, self)
-    out_bd.constructed = True
+    out_bd = self.new_result(kd_shape, out_dtype,
+                             default_divisions(self.world, kd_shape))
     self.backend.fill_container(out_bd, self, -1)
     core = self.core_box(out_bd, self.rank)
     # running best values, shaped like the rank's result core box; a slot's
@@ -1301,28 +1194,14 @@ def arg_reduce_op(self, arr, axis, kind, skipna):
     best = self.backend.new_message_buffer(box_shape(core), bd.dtype) \
         if core is not None else None
 
-    # combining exchange plan (deterministic on every rank)
     axes = (axis,)
-    msgs = []
-    for r in range(self.world):
-        if lbs[r] is None:
-            continue
-        pb = _proj_box(lbs[r], axes)
-        for s in range(self.world):
-            part = box_intersect(pb, self.core_box(out_bd, s))
-            if part is not None:
-                msgs.append((s, r, part))
-    msgs.sort(key=lambda m: (m[0], m[1], tuple(m[2][0]), tuple(m[2][1])))
-
     my_pb = _proj_box(lb, axes) if lb is not None else None
 
     def mine(t, bx):
-        sl = tuple(slice(int(bx[0, i] - my_pb[0, i]),
-                         int(bx[1, i] - my_pb[0, i]) + 1) for i in range(nd))
-        return t[sl].contiguous()
+        return t[box_slices(bx, my_pb[0])].contiguous()
 
     vsends, isends, recvs, merges = [], [], [], []
-    for (dst, src, bx) in msgs:
+    for (dst, src, bx) in self.combine_plan(lbs, axes, out_bd):
         if src == self.rank and dst == self.rank:
             merges.append((bx, mine(vals, bx), mine(idxs, bx)))
             continue
@@ -1342,11 +1221,8 @@ def arg_reduce_op(self, arr, axis, kind, skipna):
         self.backend.exchange(isends, [(s, bi) for (s, _, _, bi) in recvs])
     merges.extend((bx, bv, bi) for (_, bx, bv, bi) in recvs)
     for (bx, sv, si) in merges:
-        rel = bx.copy()
-        rel[0] -= core[0]
-        rel[1] -= core[0]
-        hooks.arg_combine_box(out_bd, self, bx, best, rel, sv, si, kind,
-                              skipna)
+        hooks.arg_combine_box(out_bd, self, bx, best, box_rel(bx, core[0]),
+                              sv, si, kind, skipna)
     self.backend.free_temps()
     return out_bd
 

@@ -92,6 +92,52 @@ def box_subtract(a, b):
     return out
 
 
+def box_rel(b, origin):
+    """`b` in coordinates relative to the lo corner `origin`."""
+    return b - np.asarray(origin, dtype=np.int64)
+
+
+def box_slices(b, origin=None):
+    """Index slices selecting `b` in an array whose first cell sits at
+    `origin` (default: the global origin)."""
+    lo, hi = (b[0], b[1]) if origin is None else box_rel(b, origin)
+    return tuple(slice(int(l), int(h) + 1) for l, h in zip(lo, hi))
+
+
+def spans_trailing_axes(b, shape):
+    """True if `b` covers the full extent of every axis but the first, i.e.
+    its cells are one contiguous interval of `shape`'s C order."""
+    return all(int(b[0, d]) == 0 and int(b[1, d]) == shape[d] - 1
+               for d in range(1, len(shape)))
+
+
+def divisions_from_boxes(boxes, nd):
+    """Per-rank boxes (None = rank owns nothing) as a divisions array; an
+    empty rank is lo 0 / hi -1 on every axis."""
+    divs = np.zeros((len(boxes), 2, nd), dtype=np.int64)
+    for r, b in enumerate(boxes):
+        if b is None:
+            divs[r, 1, :] = -1
+        else:
+            divs[r] = b
+    return divs
+
+
+def c_strides(shape):
+    """Row-major element strides of `shape`."""
+    strides = [1] * len(shape)
+    for i in range(len(shape) - 2, -1, -1):
+        strides[i] = strides[i + 1] * int(shape[i + 1])
+    return tuple(strides)
+
+
+def coord_offset(coord, div_start, pads, cstrides):
+    """Element offset of base coordinate `coord` in a container whose core
+    starts at `div_start`, behind `pads` leading cells per axis."""
+    return sum((int(coord[b]) - int(div_start[b]) + int(pads[b]))
+               * int(cstrides[b]) for b in range(len(cstrides)))
+
+
 # ---------------------------------------------------------------------------
 # View
 # ---------------------------------------------------------------------------
@@ -336,9 +382,7 @@ class View:
             b, st = self.axis_map[v], self.steps[v]
             if b >= 0 and st != 0:
                 coord[b] += int(i0[v]) * st
-        off0 = 0
-        for b in range(self.base_ndim):
-            off0 += (coord[b] - int(div_start[b]) + int(border[b])) * int(cstrides[b])
+        off0 = coord_offset(coord, div_start, border, cstrides)
         strides = []
         for v in range(self.ndim):
             b, st = self.axis_map[v], self.steps[v]

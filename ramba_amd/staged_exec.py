@@ -6,7 +6,8 @@ after the first step (the staged analog of Runtime's recipe cache)."""
 
 import numpy as np
 
-from .shardview import box_shape, box_subtract
+from . import ir
+from .shardview import box_shape, box_subtract, coord_offset
 
 
 class StagedRecipe:
@@ -27,28 +28,6 @@ class StagedRecipe:
         self.E = (0, 0)
         self.residual_units = None  # built lazily on first run
         self.lds_of_writer = {}
-
-
-def adopt_and_alloc(rt, g, live):
-    """Flex adoption + allocation (mirror of _build_and_run's prologue)."""
-    eboxes = g.exec_boxes()
-    nd = len(g.shape)
-    adopted = None
-    for oi in live.values():
-        if oi.bd.is_flex and oi.bd.shape == g.shape:
-            if adopted is None:
-                adopted = np.zeros((rt.world, 2, nd), dtype=np.int64)
-                for r, b in enumerate(eboxes):
-                    if b is None:
-                        adopted[r, 1, :] = -1
-                    else:
-                        adopted[r] = b
-            oi.bd.divisions = adopted
-            oi.bd.flex = False
-    for oi in live.values():
-        if not oi.bd.constructed:
-            rt.backend.alloc_container(oi.bd, rt)
-            oi.bd.constructed = True
 
 
 def _keep_hbm_reads(g1, g2, hbm_read_gids):
@@ -73,8 +52,7 @@ def _store_vals(vals, prefix, rt, bd):
         vals[f"{prefix}_hi0"] = vals[f"{prefix}_hi1"] = 0
         return None
     vals[f"{prefix}_ptr"] = rt.backend.container_addr(bd)
-    vals[f"{prefix}_off"] = sum((pads[i] - int(d[0, i])) * cs[i]
-                                for i in range(2))
+    vals[f"{prefix}_off"] = coord_offset((0, 0), d[0], pads, cs)
     vals[f"{prefix}_s0"], vals[f"{prefix}_s1"] = cs[0], cs[1]
     return d
 
@@ -161,8 +139,7 @@ def build_vals_and_launch(rt, rec, g1, g2, live1, live2, ib2):
         d, _, cs, pads = rt.shard_geometry(bd)
         assert d is not None    # written on this rank => shard exists
         vals[f"rsrc{ri}_ptr"] = backend.container_addr(bd)
-        vals[f"rsrc{ri}_off"] = sum((pads[i] - int(d[0, i])) * cs[i]
-                                    for i in range(2))
+        vals[f"rsrc{ri}_off"] = coord_offset((0, 0), d[0], pads, cs)
         vals[f"rsrc{ri}_s0"], vals[f"rsrc{ri}_s1"] = cs[0], cs[1]
         core = rt.core_box(bd, rt.rank)
         wimg = wv.image_box(ib2)
@@ -237,8 +214,8 @@ def run_recipe(rt, rec, g1, g2, live1, dead1, live2, hbm_read_gids):
     """Fast path: re-run a cached StagedRecipe against fresh groups."""
     backend = rt.backend
     _keep_hbm_reads(g1, g2, hbm_read_gids)
-    adopt_and_alloc(rt, g1, live1)
-    adopt_and_alloc(rt, g2, live2)
+    rt.adopt_and_alloc(g1, live1)
+    rt.adopt_and_alloc(g2, live2)
     ib1 = g1.exec_boxes()[rt.rank]
     ib2 = g2.exec_boxes()[rt.rank]
     interior = None
@@ -256,10 +233,7 @@ def run_recipe(rt, rec, g1, g2, live1, dead1, live2, hbm_read_gids):
             # no local tiles: reduce this rank's whole core (if any)
             finish_staged_reductions(rt, g2)
     backend.free_temps()
-    for bd in g1.delete_bds + g2.delete_bds:
-        if bd.constructed:
-            backend.free_container(bd)
-            bd.constructed = False
+    rt.free_shards(g1.delete_bds + g2.delete_bds)
     return True
 
 
@@ -270,10 +244,9 @@ def reduce_boxes_partial(rt, bd, boxes, kind, dtype):
     """Partial reduction of identity-view `bd` over base-space `boxes`
     on this rank, via the standard fused-reduce kernel (one launch per
     box; plan cached by the backend's structural key)."""
-    from . import ir
     from .runtime import KernelPlan, OperandPlan
     backend = rt.backend
-    acc = np.asarray(ir.reduction_init(kind, dtype), dtype=dtype)[()]
+    acc = ir.reduction_identity(kind, dtype)
     d, _, cs, pads = rt.shard_geometry(bd)
     if d is None:
         return acc
@@ -295,9 +268,7 @@ def reduce_boxes_partial(rt, bd, boxes, kind, dtype):
                            np.dtype(dtype)))]
         p.reductions = [spec]
         p.dead_vars = {}
-        nd = len(bd.shape)
-        off0 = sum((int(box[0, i]) - int(d[0, i]) + pads[i]) * cs[i]
-                   for i in range(nd))
+        off0 = coord_offset(box[0], d[0], pads, cs)
         p.operands = [OperandPlan("vR", "container", bd, None, off0,
                                   tuple(cs), bd.dtype)]
         vals = backend.launch(p, None)
@@ -311,14 +282,11 @@ def finish_staged_reductions(rt, g2):
     """Fallback/no-local-tiles path: each staged-reduction partial =
     the plain reduce over this rank's whole core (the tiled path instead
     folds interior+rim in-kernel and sets the partial directly)."""
-    from . import ir
     for (src, wv, pend) in g2.staged_reductions:
         bd = src.bdarray
         core = rt.core_box(bd, rt.rank)
         if core is None:
-            pend.partial = np.asarray(
-                ir.reduction_init(pend.kind, pend.dtype),
-                dtype=pend.dtype)[()]
+            pend.partial = ir.reduction_identity(pend.kind, pend.dtype)
             continue
         pend.partial = reduce_boxes_partial(rt, bd, [core], pend.kind,
                                             pend.dtype)
