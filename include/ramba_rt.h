@@ -19,6 +19,8 @@
  *                       getborder ramba.py:1260) and gather (get_view 2160)
  *   rt_take_rows      — indexed row gather for a[int_array] / take
  *                       (all2all getitem worker, ramba.py:3960)
+ *   rt_gemm           — the local np.dot of the matmul workers
+ *                       (ramba.py:3056, 6953-7040), on the MFMA units
  *   rt_stream_sync /
  *   rt_device_sync    — worker-side completion (sync, ramba.py:9843)
  *   rt_event_*        — hot-loop timing (add_time, ramba.py:945-1022)
@@ -236,6 +238,29 @@ int rt_arg_combine_box(uintptr_t stream, void *dst_vals, void *dst_idx,
                        const int64_t *src_strides, int64_t dst_val_off,
                        int64_t dst_idx_off, int dtype, int is_max,
                        int skipna);
+
+/* Dense GEMM on the matrix units: C[M,N] (+)= A[M,K] @ B[K,N] — the local
+ * np.dot of the reference's matmul workers (ramba/ramba.py:3056,
+ * 6953-7040).  c / a / b point at element (0,0); strides are in elements;
+ * C has column stride 1 and row stride ldc >= N.  dtype: RT_F64
+ * (v_mfma_f64_16x16x4) or RT_F32 (v_mfma_f32_32x32x2).  accumulate: 0
+ * overwrites C, 1 adds to what it holds.  One 256-lane block per
+ * rt_gemm_tile() tile of C; M, N, K need not be multiples of it, and
+ * nothing outside the three matrices is read or written.  A with a_cs == 1
+ * and B with b_cs == 1 are read with 16-byte loads when base and row stride
+ * are 16-byte aligned; every other stride pattern (transposed, odd leading
+ * dimension, odd column offset) is read element-wise.  Each output element
+ * is summed in ascending k by one wave: no atomics, same bits every run.
+ * Validated before any HIP call: negative extents, extents >= 2^40, M*N,
+ * M*K or K*N above 2^46, ldc < N, dtype, accumulate, NULL pointers with
+ * work to do.  M == 0 or N == 0 returns 0 without launching; K == 0
+ * zero-fills C (accumulate 0) or leaves it (accumulate 1).
+ * rt_gemm_tile: the block tile compiled in for `dtype`; host arithmetic. */
+int rt_gemm(uintptr_t stream, void *c, const void *a, const void *b,
+            int64_t M, int64_t N, int64_t K, int64_t a_rs, int64_t a_cs,
+            int64_t b_rs, int64_t b_cs, int64_t ldc, int dtype,
+            int accumulate);
+int rt_gemm_tile(int dtype, int *bm, int *bn, int *bk);
 
 int rt_stream_sync(uintptr_t stream);
 int rt_device_sync(void);

@@ -2295,3 +2295,352 @@ extern "C" int rt_arg_combine_box(uintptr_t stream, void *dst_vals,
                                                dst_val_off, dst_idx_off, a);
     });
 }
+
+// ---------------------------------------------------------------------------
+// Dense GEMM on the matrix units: C[M,N] (+)= A[M,K] @ B[K,N], float32 and
+// float64 (the local np.dot of the reference's matmul workers,
+// ramba/ramba.py:3056, :6953-7040).
+//
+// One block of 256 lanes (4 waves, 2 x 2) owns a 128 x 128 tile of C and walks
+// K in steps of BK (64 bytes of an A row: 16 floats / 8 doubles).  Each wave
+// keeps its 64 x 64 sub-tile in accumulator registers: 2 x 2 tiles of
+// v_mfma_f32_32x32x2 or 4 x 4 tiles of v_mfma_f64_16x16x4.  The A and B
+// panels of a step go global -> registers -> LDS, LDS double-buffered; the
+// global loads of step k+1 are issued before the MFMAs of step k and stored
+// to the other buffer after them, one barrier per step.
+//
+// LDS holds both panels k-major: As[k][m] and Bs[k][n], so the MFMA operand
+// of lane l (A[l % T][l / T], B[l / T][l % T], T = 32 or 16) is a read of T
+// consecutive elements per k row.  Row strides are padded (GemmT::LDA/LDB)
+// by bank arithmetic (64 four-byte banks, 32 lanes per pass assumed; not
+// measured): fp64 rows are 16 doubles apart modulo 32, so the two k rows a
+// half-wave reads fall on disjoint banks; the fp32 A stride of 130 spreads
+// the transposing stores of the 16-byte path to a two-way collision.
+//
+// Two global-load paths per operand, picked on the host (gemm_paths):
+//   16-byte : A with a_cs == 1 (a chunk runs along k and is scattered down
+//             an LDS column), B with b_cs == 1 (a chunk runs along n and is
+//             stored whole); base and row stride 16-byte aligned.  A chunk
+//             that straddles the edge falls back to element loads.
+//   element : any strides; lanes run along m (A) / n (B).
+// Rows, columns and k outside the problem are never read and enter LDS as
+// zeros, on BOTH operands in the K tail (0 x inf from a real element would
+// otherwise reach a real output); outside rows and columns are never stored.
+// Every output element is summed by one wave in ascending k: no atomics, no
+// split-K, bit-reproducible.
+// ---------------------------------------------------------------------------
+
+namespace {
+
+enum { GEMM_BM = 128, GEMM_BN = 128, GEMM_GRID_CAP = 1 << 20 };
+
+template <typename T>
+struct GemmT;
+
+template <>
+struct GemmT<float> {
+    // 32x32x2: lane l gives A[l%32][l/32], B[l/32][l%32]; holds 16 of D
+    enum { BK = 16, VEC = 4, TM = 32, KM = 2, RPT = 16, LDA = 130, LDB = 132 };
+    typedef float acc_t __attribute__((ext_vector_type(16)));
+    typedef float vec_t __attribute__((ext_vector_type(4)));
+    static __device__ __forceinline__ acc_t mfma(float a, float b, acc_t c) {
+        return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
+    }
+    // row of D held in register r by a lane of k group lk = l / 32
+    static __device__ __forceinline__ int row(int r, int lk) {
+        return 8 * (r / 4) + 4 * lk + r % 4;
+    }
+};
+
+template <>
+struct GemmT<double> {
+    // 16x16x4: lane l gives A[l%16][l/16], B[l/16][l%16]; holds 4 of D
+    enum { BK = 8, VEC = 2, TM = 16, KM = 4, RPT = 4, LDA = 144, LDB = 144 };
+    typedef double acc_t __attribute__((ext_vector_type(4)));
+    typedef double vec_t __attribute__((ext_vector_type(2)));
+    static __device__ __forceinline__ acc_t mfma(double a, double b, acc_t c) {
+        return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
+    }
+    // row of D held in register r by a lane of k group lk = l / 16: the
+    // four registers interleave the lane groups (pinned by the exact test)
+    static __device__ __forceinline__ int row(int r, int lk) {
+        return 4 * r + lk;
+    }
+};
+
+struct GemmArgs {
+    int64_t M, N, K;
+    int64_t a_rs, a_cs, b_rs, b_cs, ldc;
+    int64_t tiles_n, ntiles;
+    int accumulate;
+};
+
+// One 16-byte chunk of VEC elements at p, of which `valid` (<= 0: none) lie
+// inside the problem; a partial chunk is read element by element.
+template <typename T>
+__device__ __forceinline__ typename GemmT<T>::vec_t gemm_chunk(
+    const T *p, int64_t valid) {
+    typedef typename GemmT<T>::vec_t vec_t;
+    constexpr int VEC = GemmT<T>::VEC;
+    vec_t v = {};
+    if (valid >= VEC) {
+        v = *reinterpret_cast<const vec_t *>(p);
+    } else {
+#pragma unroll
+        for (int i = 0; i < VEC; ++i)
+            if (i < valid) v[i] = p[i];
+    }
+    return v;
+}
+
+// Global -> registers for one k step of one operand.  r holds the thread's
+// EPT = 128 * BK / 256 elements of the 128 x BK panel.
+//   KVEC  (A, a_cs == 1): chunk c = t + 256 j covers row c / 4, k (c % 4) VEC..
+//   MNVEC (B, b_cs == 1): chunk c covers k c / CPR, columns (c % CPR) VEC..
+//   ELEM: element e = t + 256 j is (mn e % 128, k e / 128).
+// mn0 / MN: tile origin and extent along m (A) or n (B); mn_s / k_s strides.
+enum { GEMM_ELEM = 0, GEMM_KVEC = 1, GEMM_MNVEC = 2 };
+
+template <typename T, int PATH>
+__device__ __forceinline__ void gemm_load(
+    const T *__restrict__ p, int64_t mn_s, int64_t k_s, int64_t mn0,
+    int64_t MN, int64_t k0, int64_t K, int t,
+    T (&r)[GEMM_BM * GemmT<T>::BK / 256]) {
+    typedef GemmT<T> G;
+    constexpr int VEC = G::VEC, EPT = GEMM_BM * G::BK / 256;
+    static_assert(G::BK / VEC == 4, "4 chunks (64 bytes) per panel row");
+    if constexpr (PATH == GEMM_KVEC) {
+#pragma unroll
+        for (int j = 0; j < EPT / VEC; ++j) {
+            const int c = t + 256 * j;
+            const int64_t mn = mn0 + (c >> 2), k = k0 + (c & 3) * VEC;
+            typename G::vec_t v = {};
+            if (mn < MN) v = gemm_chunk<T>(p + mn * mn_s + k, K - k);
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) r[j * VEC + i] = v[i];
+        }
+    } else if constexpr (PATH == GEMM_MNVEC) {
+        constexpr int CPR = GEMM_BN / VEC;
+#pragma unroll
+        for (int j = 0; j < EPT / VEC; ++j) {
+            const int c = t + 256 * j;
+            const int64_t k = k0 + c / CPR, mn = mn0 + (c % CPR) * VEC;
+            typename G::vec_t v = {};
+            if (k < K) v = gemm_chunk<T>(p + k * k_s + mn, MN - mn);
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) r[j * VEC + i] = v[i];
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < EPT; ++j) {
+            const int e = t + 256 * j;
+            const int64_t mn = mn0 + (e & 127), k = k0 + (e >> 7);
+            r[j] = (mn < MN && k < K) ? p[mn * mn_s + k * k_s] : T(0);
+        }
+    }
+}
+
+// Registers -> the k-major LDS panel s[k * LD + mn], same element mapping.
+template <typename T, int PATH, int LD>
+__device__ __forceinline__ void gemm_stage(
+    T *s, int t, const T (&r)[GEMM_BM * GemmT<T>::BK / 256]) {
+    typedef GemmT<T> G;
+    constexpr int VEC = G::VEC, EPT = GEMM_BM * G::BK / 256;
+    if constexpr (PATH == GEMM_KVEC) {
+#pragma unroll
+        for (int j = 0; j < EPT / VEC; ++j) {
+            const int c = t + 256 * j;
+#pragma unroll
+            for (int i = 0; i < VEC; ++i)
+                s[((c & 3) * VEC + i) * LD + (c >> 2)] = r[j * VEC + i];
+        }
+    } else if constexpr (PATH == GEMM_MNVEC) {
+        constexpr int CPR = GEMM_BN / VEC;
+        static_assert((LD * sizeof(T)) % 16 == 0, "16-byte LDS rows");
+#pragma unroll
+        for (int j = 0; j < EPT / VEC; ++j) {
+            const int c = t + 256 * j;
+            typename G::vec_t v;
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) v[i] = r[j * VEC + i];
+            *reinterpret_cast<typename G::vec_t *>(
+                &s[(c / CPR) * LD + (c % CPR) * VEC]) = v;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < EPT; ++j) {
+            const int e = t + 256 * j;
+            s[(e >> 7) * LD + (e & 127)] = r[j];
+        }
+    }
+}
+
+// The kernel is compiled with the packed-fp32 VALU forms (v_pk_*_f32) off:
+// its only VALU float math is the accumulate epilogue `C + acc`, which is to
+// stay one IEEE add per element whatever the compiler's vectoriser prefers.
+// The attribute covers this function and what is inlined into it only (the
+// host pass does not know the feature, so it sees nothing).
+#if defined(__HIP_DEVICE_COMPILE__)
+#define GEMM_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define GEMM_NO_PK_F32
+#endif
+
+template <typename T, int PA, int PB>
+__global__ __launch_bounds__(256) GEMM_NO_PK_F32 void gemm_kernel(
+    T *__restrict__ c, const T *__restrict__ a, const T *__restrict__ b,
+    GemmArgs g) {
+    typedef GemmT<T> G;
+    constexpr int BK = G::BK, TM = G::TM, KM = G::KM, NT = 64 / TM;
+    constexpr int EPT = GEMM_BM * BK / 256;
+    static_assert(GEMM_BM == 128 && GEMM_BN == 128, "2 x 2 waves of 64 x 64");
+    __shared__ __attribute__((aligned(16))) T As[2][BK * G::LDA];
+    __shared__ __attribute__((aligned(16))) T Bs[2][BK * G::LDB];
+
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
+    const int lr = lane % TM, lk = lane / TM;
+    const int64_t nk = (g.K + BK - 1) / BK;
+
+    for (int64_t tile = blockIdx.x; tile < g.ntiles; tile += gridDim.x) {
+        const int64_t m0 = (tile / g.tiles_n) * GEMM_BM;
+        const int64_t n0 = (tile % g.tiles_n) * GEMM_BN;
+        typename G::acc_t acc[NT][NT];
+#pragma unroll
+        for (int i = 0; i < NT; ++i)
+#pragma unroll
+            for (int j = 0; j < NT; ++j) acc[i][j] = {};
+        T ra[EPT], rb[EPT];
+
+        gemm_load<T, PA>(a, g.a_rs, g.a_cs, m0, g.M, 0, g.K, t, ra);
+        gemm_load<T, PB>(b, g.b_cs, g.b_rs, n0, g.N, 0, g.K, t, rb);
+        gemm_stage<T, PA, G::LDA>(As[0], t, ra);
+        gemm_stage<T, PB, G::LDB>(Bs[0], t, rb);
+        __syncthreads();
+
+        int cur = 0;
+        for (int64_t kt = 0; kt < nk; ++kt) {
+            const bool more = kt + 1 < nk;
+            if (more) {
+                const int64_t k0 = (kt + 1) * BK;
+                gemm_load<T, PA>(a, g.a_rs, g.a_cs, m0, g.M, k0, g.K, t, ra);
+                gemm_load<T, PB>(b, g.b_cs, g.b_rs, n0, g.N, k0, g.K, t, rb);
+            }
+            const T *Ac = As[cur], *Bc = Bs[cur];
+#pragma unroll
+            for (int kk = 0; kk < BK; kk += KM) {
+                T af[NT], bf[NT];
+#pragma unroll
+                for (int i = 0; i < NT; ++i) {
+                    af[i] = Ac[(kk + lk) * G::LDA + wm + i * TM + lr];
+                    bf[i] = Bc[(kk + lk) * G::LDB + wn + i * TM + lr];
+                }
+#pragma unroll
+                for (int i = 0; i < NT; ++i)
+#pragma unroll
+                    for (int j = 0; j < NT; ++j)
+                        acc[i][j] = G::mfma(af[i], bf[j], acc[i][j]);
+            }
+            if (more) {
+                gemm_stage<T, PA, G::LDA>(As[cur ^ 1], t, ra);
+                gemm_stage<T, PB, G::LDB>(Bs[cur ^ 1], t, rb);
+            }
+            // the next step reads what was just staged, and the step after
+            // it overwrites the buffer read above
+            __syncthreads();
+            cur ^= 1;
+        }
+
+        // register r of a tile is row G::row(r, lane / T), column lane % T
+#pragma unroll
+        for (int i = 0; i < NT; ++i)
+#pragma unroll
+            for (int j = 0; j < NT; ++j)
+#pragma unroll
+                for (int r = 0; r < G::RPT; ++r) {
+                    const int64_t row = m0 + wm + i * TM + G::row(r, lk);
+                    const int64_t col = n0 + wn + j * TM + lr;
+                    if (row < g.M && col < g.N) {
+                        T *p = c + row * g.ldc + col;
+                        T v = acc[i][j][r];
+                        if (g.accumulate) v = *p + v;
+                        *p = v;
+                    }
+                }
+    }
+}
+
+// Which load path each operand takes: 16-byte when its unit stride runs
+// along the panel's fast axis and base and row stride are 16-byte aligned.
+template <typename T>
+void gemm_paths(const void *a, const void *b, const GemmArgs &g, bool *va,
+                bool *vb) {
+    const int64_t per = 16 / (int64_t)sizeof(T);
+    *va = g.a_cs == 1 && g.a_rs % per == 0
+          && reinterpret_cast<uintptr_t>(a) % 16 == 0;
+    *vb = g.b_cs == 1 && g.b_rs % per == 0
+          && reinterpret_cast<uintptr_t>(b) % 16 == 0;
+}
+
+template <typename T>
+int gemm_launch(uintptr_t stream, void *c, const void *a, const void *b,
+                const GemmArgs &g) {
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    bool va, vb;
+    gemm_paths<T>(a, b, g, &va, &vb);
+    const unsigned blocks = (unsigned)(g.ntiles < GEMM_GRID_CAP
+                                           ? g.ntiles : GEMM_GRID_CAP);
+#define GEMM_GO(PA, PB)                                                    \
+    hipLaunchKernelGGL((gemm_kernel<T, PA, PB>), dim3(blocks), dim3(256),  \
+                       0, st, static_cast<T *>(c),                         \
+                       static_cast<const T *>(a),                          \
+                       static_cast<const T *>(b), g)
+    if (va && vb) GEMM_GO(GEMM_KVEC, GEMM_MNVEC);
+    else if (va) GEMM_GO(GEMM_KVEC, GEMM_ELEM);
+    else if (vb) GEMM_GO(GEMM_ELEM, GEMM_MNVEC);
+    else GEMM_GO(GEMM_ELEM, GEMM_ELEM);
+#undef GEMM_GO
+    return launched("gemm");
+}
+
+}  // namespace
+
+extern "C" int rt_gemm_tile(int dtype, int *bm, int *bn, int *bk) {
+    const char *who = "rt_gemm_tile";
+    if (dtype != RT_F64 && dtype != RT_F32) return fail(who, "bad dtype");
+    if (!bm || !bn || !bk) return fail(who, "NULL output");
+    *bm = GEMM_BM;
+    *bn = GEMM_BN;
+    *bk = dtype == RT_F64 ? (int)GemmT<double>::BK : (int)GemmT<float>::BK;
+    return 0;
+}
+
+extern "C" int rt_gemm(uintptr_t stream, void *c, const void *a,
+                       const void *b, int64_t M, int64_t N, int64_t K,
+                       int64_t a_rs, int64_t a_cs, int64_t b_rs,
+                       int64_t b_cs, int64_t ldc, int dtype,
+                       int accumulate) {
+    const char *who = "rt_gemm";
+    if (dtype != RT_F64 && dtype != RT_F32) return fail(who, "bad dtype");
+    if (accumulate != 0 && accumulate != 1)
+        return fail(who, "bad accumulate");
+    if (M < 0 || N < 0 || K < 0) return fail(who, "negative extent (M/N/K)");
+    const int64_t lim = 1LL << 40, plim = 1LL << 46;
+    if (M >= lim || N >= lim || K >= lim)
+        return fail(who, "extent out of range (M/N/K)");
+    if ((N && M > plim / N) || (K && M > plim / K) || (N && K > plim / N))
+        return fail(who, "shape too large (M*N, M*K or K*N)");
+    if (ldc < N) return fail(who, "ldc < N");
+    if (M == 0 || N == 0) return 0;
+    if (!c) return fail(who, "NULL c");
+    if (K && (!a || !b)) return fail(who, "NULL a/b");
+    if (K == 0 && accumulate) return 0;
+    GemmArgs g;
+    g.M = M, g.N = N, g.K = K;
+    g.a_rs = a_rs, g.a_cs = a_cs, g.b_rs = b_rs, g.b_cs = b_cs, g.ldc = ldc;
+    g.tiles_n = (N + GEMM_BN - 1) / GEMM_BN;
+    g.ntiles = ((M + GEMM_BM - 1) / GEMM_BM) * g.tiles_n;
+    g.accumulate = accumulate;
+    if (dtype == RT_F64) return gemm_launch<double>(stream, c, a, b, g);
+    return gemm_launch<float>(stream, c, a, b, g);
+}

@@ -80,6 +80,10 @@ _RT_ABI = {
                            _int, _int, _int, _i64, _vp, _vp, _vp, _vp]),
     "rt_arg_combine_box": (_int, [_sz, _vp, _vp, _vp, _vp, _int, _p64, _p64,
                                   _p64, _p64, _i64, _i64, _int, _int, _int]),
+    "rt_gemm": (_int, [_sz, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
+                       _i64, _i64, _i64, _int, _int]),
+    "rt_gemm_tile": (_int, [_int, ctypes.POINTER(_int), ctypes.POINTER(_int),
+                            ctypes.POINTER(_int)]),
     "rt_stream_sync": (_int, [_sz]),
     "rt_device_sync": (_int, []),
     "rt_event_create": (_int, [_pvp]),
@@ -919,6 +923,50 @@ class HipBackend:
                           _hb_take_dense_side(dense), tuple(out_bd.shape[1:]),
                           None, positions.contiguous(), int(dense.shape[0]),
                           dense.element_size())
+
+    # -- dense matmul (runtime.matmul_op) -------------------------------------
+    #
+    # The two hooks of ramba_amd/gemm.py on the rt_gemm MFMA kernel.  A and C
+    # are read and written in place in their containers; the k range of A is
+    # a pointer offset, never a copy.
+
+    def gemm_tile(self, dtype):
+        """(BM, BN, BK): the block tile rt_gemm was compiled with."""
+        bm, bn, bk = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        self._check(self.lib.rt_gemm_tile(
+            RT_DTYPE[str(np.dtype(dtype))], ctypes.byref(bm),
+            ctypes.byref(bn), ctypes.byref(bk)), "rt_gemm_tile")
+        return bm.value, bn.value, bk.value
+
+    def gemm_panel(self, b_bd, rt):
+        """The rank's rows of B as a (rows, N) device tensor: dense, so it
+        can be sent, except at world 1, where nothing is sent and rt_gemm
+        reads the container core in place through its strides."""
+        core = rt.core_box(b_bd, rt.rank)
+        if core is None:
+            return self.new_message_buffer((0, b_bd.shape[1]), b_bd.dtype)
+        if rt.world == 1:
+            _, _, _, pads = rt.shard_geometry(b_bd)
+            return self._cont(b_bd)[tuple(
+                slice(p, p + s) for p, s in zip(pads, box_shape(core)))]
+        return self.pack_box(b_bd, rt, core)
+
+    def gemm_local(self, c_bd, rt, a_bd, k0, k1, panel, accumulate):
+        """core(C) (+)= core(A)[:, k0:k1] @ panel, one rt_gemm launch."""
+        if rt.core_box(a_bd, rt.rank) is None:
+            return
+        aptr, (a_cs,), a_rs, m = self._take_cont_side(a_bd, rt)
+        cptr, (c_cs,), ldc, cm = self._take_cont_side(c_bd, rt)
+        n = int(c_bd.shape[1])
+        assert cm == m and c_cs == 1 and tuple(panel.shape) == (k1 - k0, n)
+        es = panel.element_size()
+        self._check(self.lib.rt_gemm(
+            self._stream(), ctypes.c_void_p(cptr),
+            ctypes.c_void_p(aptr + k0 * a_cs * es),
+            ctypes.c_void_p(panel.data_ptr()), m, n, k1 - k0, a_rs, a_cs,
+            panel.stride(0), panel.stride(1), ldc,
+            RT_DTYPE[str(np.dtype(c_bd.dtype))], int(bool(accumulate))),
+            "rt_gemm")
 
     # -- argmax / argmin pair reductions (runtime.arg_reduce_op) --------------
     #

@@ -1424,19 +1424,43 @@ def expand_dims(a, axis):
     return a[idx]
 
 
-def matmul(a, b):
-    """reference matmul (ramba.py:6953): every case lowers to the
-    broadcast-views × fused-multiply × axis-sum composition the reference
-    itself uses for its N-D path (`(a*b).sum(axis=-2)`).  The K-axis
-    product is materialised before the axis reduction (no dense-GEMM MFMA
-    path — `north_star` has no dense contraction in scope), so this is
-    meant for the reference's moderate-size matmul uses, not as a BLAS."""
-    if isinstance(a, np.ndarray):
-        a = fromarray(a)
-    if isinstance(b, np.ndarray):
-        b = fromarray(b)
-    if not isinstance(a, ndarray) or not isinstance(b, ndarray):
-        raise ValueError("matmul cannot be used with scalar arguments")
+def _gemm_operand(x, dtype, rt):
+    """`x` (2-D) as a constructed, identity-view array of `dtype` on
+    contiguous_divisions: itself when it already is one, else a copy (and
+    cast) through the fused engine."""
+    bd = x.bdarray
+    cdivs = contiguous_divisions(rt.world, x.shape)
+    if (x.dtype == dtype and bd.constructed
+            and x.view.is_identity_for(bd.shape)
+            and np.array_equal(bd.divisions, cdivs)):
+        return x
+    t_bd = deferred.bdarray(x.shape, dtype, cdivs, default_border, flex=False)
+    tmp = ndarray(t_bd, View.identity(x.shape))
+    deferred.add_op(tmp, "=", x if x.dtype == dtype else ir.Cast(x, dtype),
+                    empty_like=empty_like)
+    return tmp
+
+
+def _matmul_gemm(a, b, dtype):
+    """2-D @ 2-D in float32 / float64 on the rt_gemm MFMA kernel
+    (runtime.matmul_op)."""
+    (m, k), n = a.shape, b.shape[1]
+    if 0 in (m, k, n):
+        return zeros((m, n), dtype=dtype)
+    rt = deferred.get_runtime()
+    deferred.flush()        # pending operands become constructed arrays
+    # (the wrappers keep temporary copies' shards alive across the multiply)
+    a, b = _gemm_operand(a, dtype, rt), _gemm_operand(b, dtype, rt)
+    deferred.flush()
+    out_bd = rt.matmul_op(a.bdarray, b.bdarray)
+    return ndarray(out_bd, View.identity(out_bd.shape))
+
+
+def _matmul_composed(a, b):
+    """matmul as broadcast views × fused multiply × axis sum, the
+    composition the reference uses for its N-D path (`(a*b).sum(axis=-2)`).
+    The K-axis product is materialised before the reduction (M·K·N elements
+    for 2-D @ 2-D)."""
     ashape, bshape = a.shape, b.shape
     if a.ndim == 1 and b.ndim == 1:
         if ashape[0] != bshape[0]:
@@ -1458,6 +1482,26 @@ def matmul(a, b):
     shp = np.broadcast_shapes(ashape[:-2], bshape[:-2]) \
         + ashape[-2:-1] + bshape[-2:]
     return (aa.broadcast_to(shp) * bb.broadcast_to(shp)).sum(axis=-2)
+
+
+def matmul(a, b):
+    """reference matmul (ramba.py:6953).  2-D @ 2-D with a float32 or
+    float64 result type is a dense GEMM on the matrix units: each rank
+    multiplies its rows of A by row panels of B that travel round a ring
+    (`runtime.matmul_op`, the rt_gemm kernel), with no M·K·N temporary.
+    Every other case (integer and bool operands, 1-D operands, batched
+    N-D) lowers to `_matmul_composed`."""
+    if isinstance(a, np.ndarray):
+        a = fromarray(a)
+    if isinstance(b, np.ndarray):
+        b = fromarray(b)
+    if not isinstance(a, ndarray) or not isinstance(b, ndarray):
+        raise ValueError("matmul cannot be used with scalar arguments")
+    if a.ndim == 2 and b.ndim == 2 and a.shape[1] == b.shape[0]:
+        dtype = np.result_type(a.dtype, b.dtype)
+        if dtype in (np.float32, np.float64):
+            return _matmul_gemm(a, b, np.dtype(dtype))
+    return _matmul_composed(a, b)
 
 
 def _nd_matmul(self, rhs):

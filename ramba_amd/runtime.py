@@ -1130,6 +1130,75 @@ def take_op(self, src_bd, idx_bd):
 Runtime.take_op = take_op
 
 # ---------------------------------------------------------------------------
+# dense 2-D matmul (reference matmul, ramba.py:6953-7040, whose workers run
+# np.dot on local panels, ramba.py:3056).  A is split over M, B over K, and C
+# over M like A, all on contiguous_divisions, so a rank's rows of C need its
+# own rows of A and ALL of B.  B's row panels travel round a ring: at step t
+# rank r multiplies the columns [k0, k1) of its A rows by the panel of rank
+# (r + t) % W, whose k range comes from B's divisions.  Step 0 is the rank's
+# own panel and overwrites C; later steps accumulate, so every element of C
+# is summed in one fixed order.  The panel for step t + 1 is posted before
+# the kernel of step t, so the wire is busy while the matrix units are.  Both
+# ends know every buffer's length from the divisions; ranks without rows of
+# A still send, ranks without rows of B send nothing and are never waited on.
+# ---------------------------------------------------------------------------
+
+
+def matmul_op(self, a_bd, b_bd):
+    from . import gemm as _gemm
+    (M, K), (K2, N) = a_bd.shape, b_bd.shape
+    assert K == K2 and a_bd.dtype == b_bd.dtype
+    W, me = self.world, self.rank
+    for bd in (a_bd, b_bd):
+        assert bd.constructed and np.array_equal(
+            bd.divisions, contiguous_divisions(W, bd.shape)), \
+            "matmul_op: operands must sit on contiguous_divisions " \
+            "(frontend repartitions first)"
+    out_bd = self.new_result((M, N), a_bd.dtype,
+                             contiguous_divisions(W, (M, N)))
+    assert np.array_equal(out_bd.divisions[:, :, 0], a_bd.divisions[:, :, 0])
+
+    def krange(r):
+        d = b_bd.divisions[r]
+        return int(d[0, 0]), int(d[1, 0]) + 1       # empty: k1 <= k0
+
+    hooks = _gemm.hooks_for(self.backend)
+    begin = getattr(self.backend, "exchange_begin", None)
+
+    def post(t, mine):
+        """Start the exchange of ring step t; returns (buffer, token)."""
+        dst, src = (me - t) % W, (me + t) % W
+        k0, k1 = krange(src)
+        sends = [(dst, mine)] if mine.shape[0] else []
+        buf = self.backend.new_message_buffer((max(k1 - k0, 0), N),
+                                              a_bd.dtype)
+        recvs = [(src, buf)] if k1 > k0 else []
+        if begin is None:
+            self.backend.exchange(sends, recvs)
+            return buf, None
+        return buf, begin(sends, recvs)
+
+    mine = hooks.gemm_panel(b_bd, self)
+    panel, first = mine, True
+    nxt = post(1, mine) if W > 1 else None
+    for t in range(W):
+        k0, k1 = krange((me + t) % W)
+        if t:
+            panel, token = nxt
+            if begin is not None:
+                self.backend.exchange_finish(token)
+            nxt = post(t + 1, mine) if t + 1 < W else None
+        if k1 > k0 or first:
+            # (an empty first panel still zero-fills C: K == 0 overwrite)
+            hooks.gemm_local(out_bd, self, a_bd, k0, max(k1, k0), panel,
+                             not first)
+            first = False
+    return out_bd
+
+
+Runtime.matmul_op = matmul_op
+
+# ---------------------------------------------------------------------------
 # argmax / argmin / nanargmax / nanargmin (the reference lists them as
 # to-do, ramba/ramba.py:10288).  A (value, index) pair is carried through
 # the local kernel tree and the cross-rank combine.  Every rank reports
