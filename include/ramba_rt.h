@@ -21,6 +21,8 @@
  *                       (all2all getitem worker, ramba.py:3960)
  *   rt_gemm           — the local np.dot of the matmul workers
  *                       (ramba.py:3056, 6953-7040), on the MFMA units
+ *   rt_gemm_batched   — the same for N-D (batched) operands
+ *   rt_gemv           — the same for one 1-D operand (A @ x, x @ A)
  *   rt_stream_sync /
  *   rt_device_sync    — worker-side completion (sync, ramba.py:9843)
  *   rt_event_*        — hot-loop timing (add_time, ramba.py:945-1022)
@@ -261,6 +263,61 @@ int rt_gemm(uintptr_t stream, void *c, const void *a, const void *b,
             int64_t b_rs, int64_t b_cs, int64_t ldc, int dtype,
             int accumulate);
 int rt_gemm_tile(int dtype, int *bm, int *bn, int *bk);
+
+/* A batch of GEMMs in one launch: for i in [0, batch),
+ * C_i[M,N] (+)= A_i[M,K] @ B_i[K,N] with X_i = x + i * x_bs (batch strides
+ * in elements).  a_bs or b_bs may be 0: that operand is shared by every
+ * entry.  c_bs must be at least (M-1)*ldc + N when batch > 1, so the
+ * results cannot overlap.  The kernel, the tile and every rule of rt_gemm
+ * hold (rt_gemm is the batch == 1 call of the same launch path); blocks walk
+ * batch x tiles tile indices, batch-major.  An operand takes 16-byte loads
+ * only if its batch stride is 16-byte aligned too.  Validated in addition:
+ * negative batch, batch >= 2^40, batch*M*N, batch*M*K or batch*K*N above
+ * 2^46 (shared operands included), c_bs.  batch == 0 returns 0 without
+ * launching. */
+int rt_gemm_batched(uintptr_t stream, void *c, const void *a, const void *b,
+                    int64_t batch, int64_t M, int64_t N, int64_t K,
+                    int64_t a_rs, int64_t a_cs, int64_t b_rs, int64_t b_cs,
+                    int64_t ldc, int64_t a_bs, int64_t b_bs, int64_t c_bs,
+                    int dtype, int accumulate);
+
+/* Matrix-vector product y[M] (+)= A[M,K] @ x[K], RT_F32 or RT_F64 — the
+ * 1-D operand forms of the reference's matmul (ramba/ramba.py:6953-7040).
+ * y / a / x point at element 0; all strides are in elements and arbitrary;
+ * x @ A is the same call on A's transposed strides.  The kernel ("regime")
+ * follows A's unit stride so that A is read once, coalesced:
+ *   0 ROW_VEC   a_cs == 1, base and a_rs 16-byte aligned: a wave per 4 rows,
+ *               lanes walk k with 16-byte loads, shuffle-tree reduction
+ *   1 ROW_ELEM  a_cs == 1 otherwise: the same with element loads
+ *   2 COL_VEC   a_rs == 1, base and a_cs 16-byte aligned: lanes along m,
+ *               16 bytes (VEC outputs) per thread, VEC thread groups
+ *               interleaved over k and summed through LDS in group order
+ *   3 COL_ELEM  anything else: one output per thread, general strides
+ * A block stages k_step elements of x in LDS and shares them among its
+ * rows_per_block outputs (rt_gemv_geometry; host arithmetic).
+ * ksplit >= 1 cuts K into ksplit ranges of ceil(K / ksplit) rounded up to
+ * k_step (trailing ranges may be empty and are not launched); with
+ * ksplit > 1 the blocks write partial sums to scratch (ksplit * M elements
+ * of the dtype, caller-owned) and a second kernel adds the ranges in
+ * ascending order.  No atomics: (shape, strides, ksplit) fixes the bits.
+ * accumulate: 0 overwrites y, 1 adds to it.  Nothing outside A, x, y and
+ * scratch is touched; lanes past an edge skip the multiply.
+ * Validated before any HIP call: dtype, negative extents, extents >= 2^40,
+ * M*K above 2^46, accumulate, ksplit < 1 or > 4096, ksplit > 1 with NULL
+ * scratch, NULL y / a / x with work to do.  M == 0 returns 0 without
+ * launching; K == 0 zero-fills y (accumulate 0) or leaves it (1).
+ * rt_gemv_plan: the regime rt_gemv will take for these arguments and the
+ * ksplit to pass: above 1 when the row blocks alone give a chip of `cus`
+ * compute units fewer than 4 blocks each, as far as every range keeps two
+ * k steps.  Host arithmetic; `cus` is an argument so that it stays so. */
+int rt_gemv(uintptr_t stream, void *y, const void *a, const void *x,
+            int64_t M, int64_t K, int64_t a_rs, int64_t a_cs, int64_t x_s,
+            int64_t y_s, int dtype, int accumulate, int64_t ksplit,
+            void *scratch);
+int rt_gemv_geometry(int dtype, int regime, int *rows_per_block, int *k_step);
+int rt_gemv_plan(const void *a, int64_t M, int64_t K, int64_t a_rs,
+                 int64_t a_cs, int dtype, int cus, int *regime,
+                 int64_t *ksplit);
 
 int rt_stream_sync(uintptr_t stream);
 int rt_device_sync(void);

@@ -2328,6 +2328,11 @@ extern "C" int rt_arg_combine_box(uintptr_t stream, void *dst_vals,
 // otherwise reach a real output); outside rows and columns are never stored.
 // Every output element is summed by one wave in ascending k: no atomics, no
 // split-K, bit-reproducible.
+//
+// A batch of products (rt_gemm_batched) is the same kernel over batch x tiles
+// tile indices, batch-major: tile index / tiles is the batch entry, whose
+// a_bs / b_bs / c_bs element offsets move the three base pointers (0: the
+// operand is shared by every entry).  rt_gemm is the batch == 1 call.
 // ---------------------------------------------------------------------------
 
 namespace {
@@ -2371,7 +2376,8 @@ struct GemmT<double> {
 struct GemmArgs {
     int64_t M, N, K;
     int64_t a_rs, a_cs, b_rs, b_cs, ldc;
-    int64_t tiles_n, ntiles;
+    int64_t a_bs, b_bs, c_bs;       // batch strides (elements)
+    int64_t batch, ntiles;          // ntiles = batch * tiles of one entry
     int accumulate;
 };
 
@@ -2486,9 +2492,16 @@ __device__ __forceinline__ void gemm_stage(
 #define GEMM_NO_PK_F32
 #endif
 
+// A block-uniform 64-bit value, held in scalar registers.
+__device__ __forceinline__ int64_t gemm_uniform(int64_t v) {
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
+    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
 template <typename T, int PA, int PB>
 __global__ __launch_bounds__(256) GEMM_NO_PK_F32 void gemm_kernel(
-    T *__restrict__ c, const T *__restrict__ a, const T *__restrict__ b,
+    T *__restrict__ c0, const T *__restrict__ a0, const T *__restrict__ b0,
     GemmArgs g) {
     typedef GemmT<T> G;
     constexpr int BK = G::BK, TM = G::TM, KM = G::KM, NT = 64 / TM;
@@ -2501,10 +2514,19 @@ __global__ __launch_bounds__(256) GEMM_NO_PK_F32 void gemm_kernel(
     const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
     const int lr = lane % TM, lk = lane / TM;
     const int64_t nk = (g.K + BK - 1) / BK;
+    const int64_t tiles_n = (g.N + GEMM_BN - 1) / GEMM_BN;
+    const int64_t tiles = (g.M + GEMM_BM - 1) / GEMM_BM * tiles_n;
 
     for (int64_t tile = blockIdx.x; tile < g.ntiles; tile += gridDim.x) {
-        const int64_t m0 = (tile / g.tiles_n) * GEMM_BM;
-        const int64_t n0 = (tile % g.tiles_n) * GEMM_BN;
+        // (block-uniform, but the 64-bit division runs on the vector unit:
+        // moved to scalar registers so the offsets below cost no VGPRs)
+        const int64_t bi = gemm_uniform(tile / tiles);
+        const int64_t bt = gemm_uniform(tile % tiles);
+        const int64_t m0 = (bt / tiles_n) * GEMM_BM;
+        const int64_t n0 = (bt % tiles_n) * GEMM_BN;
+        const T *__restrict__ a = a0 + bi * g.a_bs;
+        const T *__restrict__ b = b0 + bi * g.b_bs;
+        T *__restrict__ c = c0 + bi * g.c_bs;
         typename G::acc_t acc[NT][NT];
 #pragma unroll
         for (int i = 0; i < NT; ++i)
@@ -2571,14 +2593,16 @@ __global__ __launch_bounds__(256) GEMM_NO_PK_F32 void gemm_kernel(
 }
 
 // Which load path each operand takes: 16-byte when its unit stride runs
-// along the panel's fast axis and base and row stride are 16-byte aligned.
+// along the panel's fast axis and base, row stride and (with more than one
+// batch entry) batch stride are 16-byte aligned.
 template <typename T>
 void gemm_paths(const void *a, const void *b, const GemmArgs &g, bool *va,
                 bool *vb) {
     const int64_t per = 16 / (int64_t)sizeof(T);
-    *va = g.a_cs == 1 && g.a_rs % per == 0
+    const bool many = g.batch > 1;
+    *va = g.a_cs == 1 && g.a_rs % per == 0 && !(many && g.a_bs % per)
           && reinterpret_cast<uintptr_t>(a) % 16 == 0;
-    *vb = g.b_cs == 1 && g.b_rs % per == 0
+    *vb = g.b_cs == 1 && g.b_rs % per == 0 && !(many && g.b_bs % per)
           && reinterpret_cast<uintptr_t>(b) % 16 == 0;
 }
 
@@ -2603,6 +2627,48 @@ int gemm_launch(uintptr_t stream, void *c, const void *a, const void *b,
     return launched("gemm");
 }
 
+// Validation and launch behind rt_gemm (batch 1) and rt_gemm_batched.
+int gemm_run(const char *who, uintptr_t stream, void *c, const void *a,
+             const void *b, int64_t batch, int64_t M, int64_t N, int64_t K,
+             int64_t a_rs, int64_t a_cs, int64_t b_rs, int64_t b_cs,
+             int64_t ldc, int64_t a_bs, int64_t b_bs, int64_t c_bs, int dtype,
+             int accumulate) {
+    if (dtype != RT_F64 && dtype != RT_F32) return fail(who, "bad dtype");
+    if (accumulate != 0 && accumulate != 1)
+        return fail(who, "bad accumulate");
+    if (batch < 0) return fail(who, "negative batch");
+    if (M < 0 || N < 0 || K < 0) return fail(who, "negative extent (M/N/K)");
+    const int64_t lim = 1LL << 40, plim = 1LL << 46;
+    if (batch >= lim) return fail(who, "batch out of range");
+    if (M >= lim || N >= lim || K >= lim)
+        return fail(who, "extent out of range (M/N/K)");
+    if ((N && M > plim / N) || (K && M > plim / K) || (N && K > plim / N))
+        return fail(who, "shape too large (M*N, M*K or K*N)");
+    // (each product is at most 2^46 here, so the divisions are exact enough)
+    if (batch && ((M * N && batch > plim / (M * N))
+                  || (M * K && batch > plim / (M * K))
+                  || (K * N && batch > plim / (K * N))))
+        return fail(who, "batch too large (batch*M*N, batch*M*K or "
+                         "batch*K*N)");
+    if (ldc < N) return fail(who, "ldc < N");
+    if (batch > 1 && M && N && c_bs < (M - 1) * ldc + N)
+        return fail(who, "c_bs < (M-1)*ldc + N");
+    if (batch == 0 || M == 0 || N == 0) return 0;
+    if (!c) return fail(who, "NULL c");
+    if (K && (!a || !b)) return fail(who, "NULL a/b");
+    if (K == 0 && accumulate) return 0;
+    GemmArgs g;
+    g.M = M, g.N = N, g.K = K;
+    g.a_rs = a_rs, g.a_cs = a_cs, g.b_rs = b_rs, g.b_cs = b_cs, g.ldc = ldc;
+    g.a_bs = a_bs, g.b_bs = b_bs, g.c_bs = c_bs;
+    g.batch = batch;
+    g.ntiles = batch * ((M + GEMM_BM - 1) / GEMM_BM)
+               * ((N + GEMM_BN - 1) / GEMM_BN);
+    g.accumulate = accumulate;
+    if (dtype == RT_F64) return gemm_launch<double>(stream, c, a, b, g);
+    return gemm_launch<float>(stream, c, a, b, g);
+}
+
 }  // namespace
 
 extern "C" int rt_gemm_tile(int dtype, int *bm, int *bn, int *bk) {
@@ -2615,32 +2681,375 @@ extern "C" int rt_gemm_tile(int dtype, int *bm, int *bn, int *bk) {
     return 0;
 }
 
+extern "C" int rt_gemm_batched(uintptr_t stream, void *c, const void *a,
+                               const void *b, int64_t batch, int64_t M,
+                               int64_t N, int64_t K, int64_t a_rs,
+                               int64_t a_cs, int64_t b_rs, int64_t b_cs,
+                               int64_t ldc, int64_t a_bs, int64_t b_bs,
+                               int64_t c_bs, int dtype, int accumulate) {
+    return gemm_run("rt_gemm_batched", stream, c, a, b, batch, M, N, K, a_rs,
+                    a_cs, b_rs, b_cs, ldc, a_bs, b_bs, c_bs, dtype,
+                    accumulate);
+}
+
 extern "C" int rt_gemm(uintptr_t stream, void *c, const void *a,
                        const void *b, int64_t M, int64_t N, int64_t K,
                        int64_t a_rs, int64_t a_cs, int64_t b_rs,
                        int64_t b_cs, int64_t ldc, int dtype,
                        int accumulate) {
-    const char *who = "rt_gemm";
+    return gemm_run("rt_gemm", stream, c, a, b, 1, M, N, K, a_rs, a_cs, b_rs,
+                    b_cs, ldc, 0, 0, 0, dtype, accumulate);
+}
+
+
+// ---------------------------------------------------------------------------
+// Matrix-vector product: y[M] (+)= A[M,K] @ x[K], float32 and float64; x @ A
+// is the same call on A's transposed strides.  The kernels are bound by
+// reading A once, so each orientation gets lanes running along A's unit
+// stride (regimes, picked on the host by gemv_regime):
+//
+//   ROW_VEC / ROW_ELEM (a_cs == 1, the reduction runs along the unit stride):
+//     a block of 4 waves owns GEMV_ROW_R = 16 rows, one wave per 4 rows.  The
+//     block stages GEMV_ROW_S = 1024 elements of x in LDS once per k step;
+//     the wave's lanes walk the step 16 bytes at a time (ROW_VEC: base and
+//     row stride 16-byte aligned) or one element at a time (ROW_ELEM), each
+//     lane loading from its 4 rows before it multiplies, and keep 4 private
+//     sums.  A fixed shuffle tree (offsets 32 .. 1) finishes each row.
+//   COL_VEC / COL_ELEM (lanes along m; the reduction runs across rows of
+//     memory): a block owns GEMV_COL_R = 256 outputs and stages GEMV_COL_S =
+//     256 elements of x per step.  COL_VEC (a_rs == 1, base and a_cs 16-byte
+//     aligned): a thread owns VEC consecutive outputs (one 16-byte load per
+//     k), so 256 / VEC threads cover the outputs and the VEC thread groups
+//     interleave over k; group 0 adds the other groups' sums from LDS in
+//     ascending group order.  COL_ELEM: one output per thread, any strides
+//     (the untuned general case, and a_rs == 1 without alignment).
+//
+// K-split: blockIdx.y = range r covers k in [r klen, (r + 1) klen), klen =
+// ceil(K / ksplit) rounded up to the k step; only the ceil(K / klen)
+// non-empty ranges are launched.  With ksplit > 1 a block writes its sums to
+// scratch[r M + m] and gemv_finish_kernel adds the ranges in ascending order
+// (and applies accumulate).  No atomics anywhere: (shape, strides, ksplit)
+// fixes the summation order, hence the bits.  Lanes past the end of a row, a
+// k range or M skip the multiply, so no fill value ever meets an operand.
+// ---------------------------------------------------------------------------
+
+namespace {
+
+enum { GEMV_ROW_R = 16, GEMV_ROW_S = 1024, GEMV_COL_R = 256, GEMV_COL_S = 256,
+       GEMV_MAX_SPLIT = 4096, GEMV_GRID_CAP = 1 << 20 };
+enum { GEMV_ROW_VEC = 0, GEMV_ROW_ELEM = 1, GEMV_COL_VEC = 2,
+       GEMV_COL_ELEM = 3 };
+
+struct GemvArgs {
+    int64_t M, K, a_rs, a_cs, x_s, y_s;
+    int64_t klen;           // k per blockIdx.y, a multiple of the k step
+    int accumulate, split;  // split: sums go to part[blockIdx.y * M + m]
+};
+
+// VEC elements at p: one 16-byte load (VEC > 1) or one element.
+template <typename T, int VEC>
+__device__ __forceinline__ void gemv_ld(const T *p, T (&v)[VEC]) {
+    if constexpr (VEC == 1) {
+        v[0] = *p;
+    } else {
+        typedef T vec_t __attribute__((ext_vector_type(VEC)));
+        const vec_t w = *reinterpret_cast<const vec_t *>(p);
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) v[i] = w[i];
+    }
+}
+
+template <typename T>
+__device__ __forceinline__ void gemv_store(T *y, T *part, const GemvArgs &g,
+                                           int64_t m, T v) {
+    if (g.split) {
+        part[(int64_t)blockIdx.y * g.M + m] = v;
+    } else {
+        T *p = y + m * g.y_s;
+        *p = g.accumulate ? *p + v : v;
+    }
+}
+
+// One k step of one wave of the row kernel: ap = its first row at the
+// step's first k, n = valid k in the step, nrow = valid rows.  FULL: n and
+// nrow are whole, no test inside.  Both forms add in the same order.
+template <typename T, int VEC, bool FULL>
+__device__ __forceinline__ void gemv_row_step(
+    const T *__restrict__ ap, int64_t a_rs, const T *xs, int lane, int n,
+    int nrow, T (&acc)[GEMV_ROW_R / 4]) {
+    constexpr int RW = GEMV_ROW_R / 4;
+#pragma unroll 4
+    for (int j = 0; j < GEMV_ROW_S / (64 * VEC); ++j) {
+        const int kk = (j * 64 + lane) * VEC;
+        const int valid = FULL ? VEC : n - kk;
+        if (valid >= VEC) {
+            T xv[VEC], av[RW][VEC];
+            gemv_ld<T, VEC>(xs + kk, xv);
+#pragma unroll
+            for (int r = 0; r < RW; ++r)
+                if (FULL || r < nrow)
+                    gemv_ld<T, VEC>(ap + r * a_rs + kk, av[r]);
+#pragma unroll
+            for (int r = 0; r < RW; ++r)
+                if (FULL || r < nrow)
+#pragma unroll
+                    for (int i = 0; i < VEC; ++i) acc[r] += av[r][i] * xv[i];
+        } else {
+#pragma unroll
+            for (int r = 0; r < RW; ++r)
+                if (r < nrow)
+#pragma unroll
+                    for (int i = 0; i < VEC; ++i)
+                        if (i < valid)
+                            acc[r] += ap[r * a_rs + kk + i] * xs[kk + i];
+        }
+    }
+}
+
+template <typename T, bool VECP>
+__global__ __launch_bounds__(256) GEMM_NO_PK_F32 void gemv_row_kernel(
+    T *__restrict__ y, const T *__restrict__ a, const T *__restrict__ x,
+    T *__restrict__ part, GemvArgs g) {
+    constexpr int VEC = VECP ? 16 / (int)sizeof(T) : 1;
+    constexpr int RW = GEMV_ROW_R / 4, S = GEMV_ROW_S;
+    __shared__ __attribute__((aligned(16))) T xs[S];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int64_t kb = (int64_t)blockIdx.y * g.klen;
+    const int64_t ke = kb + g.klen < g.K ? kb + g.klen : g.K;
+    const int64_t nrb = (g.M + GEMV_ROW_R - 1) / GEMV_ROW_R;
+    for (int64_t rb = blockIdx.x; rb < nrb; rb += gridDim.x) {
+        const int64_t r0 = rb * GEMV_ROW_R + wave * RW;
+        const int nrow = r0 >= g.M ? 0 : g.M - r0 < RW ? (int)(g.M - r0) : RW;
+        T acc[RW];
+#pragma unroll
+        for (int r = 0; r < RW; ++r) acc[r] = T(0);
+        for (int64_t k0 = kb; k0 < ke; k0 += S) {
+            const int n = ke - k0 < S ? (int)(ke - k0) : S;
+            for (int i = t; i < n; i += 256) xs[i] = x[(k0 + i) * g.x_s];
+            __syncthreads();
+            if (nrow > 0) {
+                const T *ap = a + r0 * g.a_rs + k0;
+                if (n == S && nrow == RW)
+                    gemv_row_step<T, VEC, true>(ap, g.a_rs, xs, lane, n, nrow,
+                                                acc);
+                else
+                    gemv_row_step<T, VEC, false>(ap, g.a_rs, xs, lane, n,
+                                                 nrow, acc);
+            }
+            __syncthreads();        // the next step overwrites xs
+        }
+#pragma unroll
+        for (int r = 0; r < RW; ++r) {
+            T v = acc[r];
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+            if (lane == 0 && r < nrow) gemv_store<T>(y, part, g, r0 + r, v);
+        }
+    }
+}
+
+template <typename T, bool VECP>
+__global__ __launch_bounds__(256) GEMM_NO_PK_F32 void gemv_col_kernel(
+    T *__restrict__ y, const T *__restrict__ a, const T *__restrict__ x,
+    T *__restrict__ part, GemvArgs g) {
+    constexpr int VEC = VECP ? 16 / (int)sizeof(T) : 1;
+    constexpr int TM = 256 / VEC, KG = VEC, R = GEMV_COL_R, S = GEMV_COL_S;
+    __shared__ T xs[S];
+    __shared__ T red[KG > 1 ? (KG - 1) * R : 1];
+    const int t = threadIdx.x, tm = t % TM, kg = t / TM;
+    const int64_t kb = (int64_t)blockIdx.y * g.klen;
+    const int64_t ke = kb + g.klen < g.K ? kb + g.klen : g.K;
+    const int64_t nrb = (g.M + R - 1) / R;
+    for (int64_t rb = blockIdx.x; rb < nrb; rb += gridDim.x) {
+        const int64_t m0 = rb * R + tm * VEC, left = g.M - m0;
+        const int mv = left >= VEC ? VEC : left > 0 ? (int)left : 0;
+        T acc[VEC];
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) acc[i] = T(0);
+        for (int64_t k0 = kb; k0 < ke; k0 += S) {
+            const int n = ke - k0 < S ? (int)(ke - k0) : S;
+            for (int i = t; i < n; i += 256) xs[i] = x[(k0 + i) * g.x_s];
+            __syncthreads();
+            if (mv == VEC) {
+                const T *ak = a + m0 * g.a_rs + k0 * g.a_cs;
+#pragma unroll 8
+                for (int kk = kg; kk < n; kk += KG) {
+                    T av[VEC];
+                    gemv_ld<T, VEC>(ak + kk * g.a_cs, av);
+                    const T xv = xs[kk];
+#pragma unroll
+                    for (int i = 0; i < VEC; ++i) acc[i] += av[i] * xv;
+                }
+            } else if (mv > 0) {    // the last outputs of M, element-wise
+                const T *ak = a + m0 * g.a_rs + k0 * g.a_cs;
+                for (int kk = kg; kk < n; kk += KG)
+#pragma unroll
+                    for (int i = 0; i < VEC; ++i)
+                        if (i < mv)
+                            acc[i] += ak[kk * g.a_cs + i * g.a_rs] * xs[kk];
+            }
+            __syncthreads();        // the next step overwrites xs
+        }
+        if constexpr (KG > 1) {
+            if (kg > 0)
+#pragma unroll
+                for (int i = 0; i < VEC; ++i)
+                    red[(kg - 1) * R + tm * VEC + i] = acc[i];
+            __syncthreads();
+            if (kg == 0)
+                for (int q = 1; q < KG; ++q)
+#pragma unroll
+                    for (int i = 0; i < VEC; ++i)
+                        acc[i] += red[(q - 1) * R + tm * VEC + i];
+            __syncthreads();        // the next row block overwrites red
+        }
+        if (kg == 0)
+#pragma unroll
+            for (int i = 0; i < VEC; ++i)
+                if (i < mv) gemv_store<T>(y, part, g, m0 + i, acc[i]);
+    }
+}
+
+// y[m] (+)= part[0][m] + part[1][m] + ...; nparts == 0 zero-fills (K == 0).
+template <typename T>
+__global__ __launch_bounds__(256) GEMM_NO_PK_F32 void gemv_finish_kernel(
+    T *__restrict__ y, const T *__restrict__ part, int64_t M, int64_t y_s,
+    int64_t nparts, int accumulate) {
+    for (int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x; m < M;
+         m += (int64_t)gridDim.x * 256) {
+        T v = T(0);
+        for (int64_t p = 0; p < nparts; ++p) v += part[p * M + m];
+        T *q = y + m * y_s;
+        *q = accumulate ? *q + v : v;
+    }
+}
+
+int gemv_regime(const void *a, int64_t a_rs, int64_t a_cs, int dtype) {
+    const int64_t per = dtype == RT_F64 ? 2 : 4;
+    const bool al = reinterpret_cast<uintptr_t>(a) % 16 == 0;
+    if (a_cs == 1)
+        return al && a_rs % per == 0 ? GEMV_ROW_VEC : GEMV_ROW_ELEM;
+    return a_rs == 1 && al && a_cs % per == 0 ? GEMV_COL_VEC : GEMV_COL_ELEM;
+}
+
+void gemv_geometry(int regime, int64_t *rows, int64_t *step) {
+    const bool row = regime == GEMV_ROW_VEC || regime == GEMV_ROW_ELEM;
+    *rows = row ? (int64_t)GEMV_ROW_R : (int64_t)GEMV_COL_R;
+    *step = row ? (int64_t)GEMV_ROW_S : (int64_t)GEMV_COL_S;
+}
+
+// The checks rt_gemv and rt_gemv_plan share.
+int gemv_check(const char *who, int64_t M, int64_t K, int dtype) {
     if (dtype != RT_F64 && dtype != RT_F32) return fail(who, "bad dtype");
+    if (M < 0 || K < 0) return fail(who, "negative extent (M/K)");
+    const int64_t lim = 1LL << 40, plim = 1LL << 46;
+    if (M >= lim || K >= lim) return fail(who, "extent out of range (M/K)");
+    if (K && M > plim / K) return fail(who, "shape too large (M*K)");
+    return 0;
+}
+
+template <typename T>
+int gemv_launch(uintptr_t stream, void *y, const void *a, const void *x,
+                void *scratch, const GemvArgs &g, int regime,
+                int64_t nparts) {
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    int64_t rows, step;
+    gemv_geometry(regime, &rows, &step);
+    const int64_t nrb = (g.M + rows - 1) / rows;
+    const dim3 grid((unsigned)(nrb < GEMV_GRID_CAP ? nrb : GEMV_GRID_CAP),
+                    (unsigned)nparts);
+#define GEMV_GO(KERNEL)                                                    \
+    hipLaunchKernelGGL((KERNEL), grid, dim3(256), 0, st,                   \
+                       static_cast<T *>(y), static_cast<const T *>(a),     \
+                       static_cast<const T *>(x), static_cast<T *>(scratch), g)
+    if (nparts == 0) {
+    } else if (regime == GEMV_ROW_VEC) {
+        GEMV_GO((gemv_row_kernel<T, true>));
+    } else if (regime == GEMV_ROW_ELEM) {
+        GEMV_GO((gemv_row_kernel<T, false>));
+    } else if (regime == GEMV_COL_VEC) {
+        GEMV_GO((gemv_col_kernel<T, true>));
+    } else {
+        GEMV_GO((gemv_col_kernel<T, false>));
+    }
+#undef GEMV_GO
+    if (g.split || nparts == 0) {
+        const int64_t fb = (g.M + 255) / 256;
+        hipLaunchKernelGGL((gemv_finish_kernel<T>),
+                           dim3((unsigned)(fb < GEMV_GRID_CAP ? fb
+                                                              : GEMV_GRID_CAP)),
+                           dim3(256), 0, st, static_cast<T *>(y),
+                           static_cast<const T *>(scratch), g.M, g.y_s,
+                           nparts, g.accumulate);
+    }
+    return launched("gemv");
+}
+
+}  // namespace
+
+extern "C" int rt_gemv_geometry(int dtype, int regime, int *rows_per_block,
+                                int *k_step) {
+    const char *who = "rt_gemv_geometry";
+    if (dtype != RT_F64 && dtype != RT_F32) return fail(who, "bad dtype");
+    if (regime < GEMV_ROW_VEC || regime > GEMV_COL_ELEM)
+        return fail(who, "bad regime");
+    if (!rows_per_block || !k_step) return fail(who, "NULL output");
+    int64_t rows, step;
+    gemv_geometry(regime, &rows, &step);
+    *rows_per_block = (int)rows;
+    *k_step = (int)step;
+    return 0;
+}
+
+extern "C" int rt_gemv_plan(const void *a, int64_t M, int64_t K, int64_t a_rs,
+                            int64_t a_cs, int dtype, int cus, int *regime,
+                            int64_t *ksplit) {
+    const char *who = "rt_gemv_plan";
+    if (gemv_check(who, M, K, dtype)) return 1;
+    if (cus < 1) return fail(who, "bad cus");
+    if (!regime || !ksplit) return fail(who, "NULL output");
+    *regime = gemv_regime(a, a_rs, a_cs, dtype);
+    int64_t rows, step;
+    gemv_geometry(*regime, &rows, &step);
+    // Split K when the row blocks alone give the chip under 4 blocks per CU,
+    // as far as every range keeps at least two k steps.
+    const int64_t nrb = (M + rows - 1) / rows, steps = (K + step - 1) / step;
+    const int64_t want = 4 * (int64_t)cus;
+    int64_t ks = 1;
+    if (nrb > 0 && nrb < want) {
+        ks = (want + nrb - 1) / nrb;
+        if (ks > steps / 2) ks = steps / 2;
+        if (ks > GEMV_MAX_SPLIT) ks = GEMV_MAX_SPLIT;
+        if (ks < 1) ks = 1;
+    }
+    *ksplit = ks;
+    return 0;
+}
+
+extern "C" int rt_gemv(uintptr_t stream, void *y, const void *a,
+                       const void *x, int64_t M, int64_t K, int64_t a_rs,
+                       int64_t a_cs, int64_t x_s, int64_t y_s, int dtype,
+                       int accumulate, int64_t ksplit, void *scratch) {
+    const char *who = "rt_gemv";
+    if (gemv_check(who, M, K, dtype)) return 1;
     if (accumulate != 0 && accumulate != 1)
         return fail(who, "bad accumulate");
-    if (M < 0 || N < 0 || K < 0) return fail(who, "negative extent (M/N/K)");
-    const int64_t lim = 1LL << 40, plim = 1LL << 46;
-    if (M >= lim || N >= lim || K >= lim)
-        return fail(who, "extent out of range (M/N/K)");
-    if ((N && M > plim / N) || (K && M > plim / K) || (N && K > plim / N))
-        return fail(who, "shape too large (M*N, M*K or K*N)");
-    if (ldc < N) return fail(who, "ldc < N");
-    if (M == 0 || N == 0) return 0;
-    if (!c) return fail(who, "NULL c");
-    if (K && (!a || !b)) return fail(who, "NULL a/b");
+    if (ksplit < 1 || ksplit > GEMV_MAX_SPLIT) return fail(who, "bad ksplit");
+    if (ksplit > 1 && !scratch) return fail(who, "NULL scratch");
+    if (M == 0) return 0;
+    if (!y) return fail(who, "NULL y");
+    if (K && (!a || !x)) return fail(who, "NULL a/x");
     if (K == 0 && accumulate) return 0;
-    GemmArgs g;
-    g.M = M, g.N = N, g.K = K;
-    g.a_rs = a_rs, g.a_cs = a_cs, g.b_rs = b_rs, g.b_cs = b_cs, g.ldc = ldc;
-    g.tiles_n = (N + GEMM_BN - 1) / GEMM_BN;
-    g.ntiles = ((M + GEMM_BM - 1) / GEMM_BM) * g.tiles_n;
-    g.accumulate = accumulate;
-    if (dtype == RT_F64) return gemm_launch<double>(stream, c, a, b, g);
-    return gemm_launch<float>(stream, c, a, b, g);
+    const int regime = gemv_regime(a, a_rs, a_cs, dtype);
+    int64_t rows, step;
+    gemv_geometry(regime, &rows, &step);
+    GemvArgs g;
+    g.M = M, g.K = K, g.a_rs = a_rs, g.a_cs = a_cs, g.x_s = x_s, g.y_s = y_s;
+    g.klen = ((K + ksplit - 1) / ksplit + step - 1) / step * step;
+    g.accumulate = accumulate, g.split = ksplit > 1;
+    const int64_t nparts = K ? (K + g.klen - 1) / g.klen : 0;
+    if (dtype == RT_F64)
+        return gemv_launch<double>(stream, y, a, x, scratch, g, regime,
+                                   nparts);
+    return gemv_launch<float>(stream, y, a, x, scratch, g, regime, nparts);
 }

@@ -84,6 +84,14 @@ _RT_ABI = {
                        _i64, _i64, _i64, _int, _int]),
     "rt_gemm_tile": (_int, [_int, ctypes.POINTER(_int), ctypes.POINTER(_int),
                             ctypes.POINTER(_int)]),
+    "rt_gemm_batched": (_int, [_sz, _vp, _vp, _vp] + [_i64] * 12
+                        + [_int, _int]),
+    "rt_gemv": (_int, [_sz, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
+                       _i64, _int, _int, _i64, _vp]),
+    "rt_gemv_geometry": (_int, [_int, _int, ctypes.POINTER(_int),
+                                ctypes.POINTER(_int)]),
+    "rt_gemv_plan": (_int, [_vp, _i64, _i64, _i64, _i64, _int, _int,
+                            ctypes.POINTER(_int), _p64]),
     "rt_stream_sync": (_int, [_sz]),
     "rt_device_sync": (_int, []),
     "rt_event_create": (_int, [_pvp]),
@@ -967,6 +975,88 @@ class HipBackend:
             panel.stride(0), panel.stride(1), ldc,
             RT_DTYPE[str(np.dtype(c_bd.dtype))], int(bool(accumulate))),
             "rt_gemm")
+
+    # -- matrix-vector and batched matmul (runtime.matvec_op / vecmat_op /
+    #    bmm_op): the hooks of ramba_amd/gemm.py on rt_gemv and
+    #    rt_gemm_batched, straight on the shard containers.
+
+    def gemv_geometry(self, dtype, regime):
+        """(rows per block, k step) of rt_gemv's kernel `regime`."""
+        r, s = ctypes.c_int(), ctypes.c_int()
+        self._check(self.lib.rt_gemv_geometry(
+            RT_DTYPE[str(np.dtype(dtype))], regime, ctypes.byref(r),
+            ctypes.byref(s)), "rt_gemv_geometry")
+        return r.value, s.value
+
+    def _gemv(self, yptr, y_s, aptr, m, k, a_rs, a_cs, x, dtype, accumulate):
+        """y (+)= A @ x, one rt_gemv call with the K-split rt_gemv_plan picks
+        for this chip; x is a 1-D device tensor."""
+        if getattr(self, "_cus", None) is None:
+            self._cus = self.torch.cuda.get_device_properties(
+                self.device).multi_processor_count
+        dt = RT_DTYPE[str(np.dtype(dtype))]
+        regime, ks = ctypes.c_int(), ctypes.c_int64()
+        self._check(self.lib.rt_gemv_plan(
+            ctypes.c_void_p(aptr), m, k, a_rs, a_cs, dt, self._cus,
+            ctypes.byref(regime), ctypes.byref(ks)), "rt_gemv_plan")
+        scratch = self.new_message_buffer((ks.value * m,), dtype) \
+            if ks.value > 1 else None
+        self._check(self.lib.rt_gemv(
+            self._stream(), ctypes.c_void_p(yptr), ctypes.c_void_p(aptr),
+            ctypes.c_void_p(x.data_ptr()), m, k, a_rs, a_cs, x.stride(0),
+            y_s, dt, int(bool(accumulate)), ks.value,
+            ctypes.c_void_p(scratch.data_ptr()) if scratch is not None
+            else None), "rt_gemv")
+
+    def gemv_vector(self, x_bd, rt):
+        """The rank's piece of a 1-D array as a device tensor (at world 1,
+        where nothing is sent, a view of the container)."""
+        core = rt.core_box(x_bd, rt.rank)
+        if core is None:
+            return self.new_message_buffer((0,), x_bd.dtype)
+        if rt.world == 1:
+            _, _, _, pads = rt.shard_geometry(x_bd)
+            return self._cont(x_bd)[pads[0]:pads[0] + int(x_bd.shape[0])]
+        return self.pack_box(x_bd, rt, core)
+
+    def gemv_local(self, y_bd, rt, a_bd, x):
+        """core(y) = core(A) @ x, x all K elements."""
+        if rt.core_box(a_bd, rt.rank) is None:
+            return
+        aptr, (a_cs,), a_rs, m = self._take_cont_side(a_bd, rt)
+        yptr, _, y_s, ym = self._take_cont_side(y_bd, rt)
+        assert ym == m and int(x.shape[0]) == a_bd.shape[1]
+        self._gemv(yptr, y_s, aptr, m, int(a_bd.shape[1]), a_rs, a_cs, x,
+                   y_bd.dtype, False)
+
+    def gemv_t_local(self, a_bd, rt, x_bd):
+        """core(x) @ core(A) as a dense length-N tensor (None: no rows)."""
+        if rt.core_box(a_bd, rt.rank) is None:
+            return None
+        aptr, (a_cs,), a_rs, k = self._take_cont_side(a_bd, rt)
+        _, _, _, pads = rt.shard_geometry(x_bd)
+        x = self._cont(x_bd)[pads[0]:pads[0] + k]
+        n = int(a_bd.shape[1])
+        out = self.new_message_buffer((n,), a_bd.dtype)
+        self._gemv(out.data_ptr(), 1, aptr, n, k, a_cs, a_rs, x, a_bd.dtype,
+                   False)
+        return out
+
+    def bgemm_local(self, c_bd, rt, a_bd, b_bd):
+        """core(C)[i] = core(A)[i] @ core(B)[i] over the rank's batch range,
+        one rt_gemm_batched launch."""
+        if rt.core_box(c_bd, rt.rank) is None:
+            return
+        aptr, (a_rs, a_cs), a_bs, nb = self._take_cont_side(a_bd, rt)
+        bptr, (b_rs, b_cs), b_bs, bnb = self._take_cont_side(b_bd, rt)
+        cptr, (ldc, c_cs), c_bs, cnb = self._take_cont_side(c_bd, rt)
+        _, m, n = c_bd.shape
+        assert nb == bnb == cnb and c_cs == 1
+        self._check(self.lib.rt_gemm_batched(
+            self._stream(), ctypes.c_void_p(cptr), ctypes.c_void_p(aptr),
+            ctypes.c_void_p(bptr), nb, int(m), int(n), int(a_bd.shape[2]),
+            a_rs, a_cs, b_rs, b_cs, ldc, a_bs, b_bs, c_bs,
+            RT_DTYPE[str(np.dtype(c_bd.dtype))], 0), "rt_gemm_batched")
 
     # -- argmax / argmin pair reductions (runtime.arg_reduce_op) --------------
     #

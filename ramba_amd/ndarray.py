@@ -1425,7 +1425,7 @@ def expand_dims(a, axis):
 
 
 def _gemm_operand(x, dtype, rt):
-    """`x` (2-D) as a constructed, identity-view array of `dtype` on
+    """`x` (any ndim) as a constructed, identity-view array of `dtype` on
     contiguous_divisions: itself when it already is one, else a copy (and
     cast) through the fused engine."""
     bd = x.bdarray
@@ -1454,6 +1454,74 @@ def _matmul_gemm(a, b, dtype):
     deferred.flush()
     out_bd = rt.matmul_op(a.bdarray, b.bdarray)
     return ndarray(out_bd, View.identity(out_bd.shape))
+
+
+def _matmul_gemv(a, b, dtype):
+    """2-D @ 1-D and 1-D @ 2-D in float32 / float64 on the rt_gemv kernels
+    (runtime.matvec_op / vecmat_op)."""
+    n = a.shape[0] if b.ndim == 1 else b.shape[1]
+    if 0 in a.shape + b.shape:
+        return zeros((n,), dtype=dtype)
+    rt = deferred.get_runtime()
+    deferred.flush()
+    a, b = _gemm_operand(a, dtype, rt), _gemm_operand(b, dtype, rt)
+    deferred.flush()
+    out_bd = rt.matvec_op(a.bdarray, b.bdarray) if b.ndim == 1 \
+        else rt.vecmat_op(a.bdarray, b.bdarray)
+    return ndarray(out_bd, View.identity(out_bd.shape))
+
+
+def _matmul_batched(a, b, dtype):
+    """N-D @ N-D (both at least 2-D, one at least 3-D) in float32 / float64:
+    the batch axes broadcast and folded into one, then one rt_gemm_batched
+    per rank (runtime.bmm_op).  The copies hold at most a broadcast operand
+    (B·K·N elements), never B·M·K·N."""
+    batch = np.broadcast_shapes(a.shape[:-2], b.shape[:-2])
+    (m, k), n = a.shape[-2:], b.shape[-1]
+    if 0 in batch + (m, k, n):
+        return zeros(batch + (m, n), dtype=dtype)
+    rt = deferred.get_runtime()
+    nb = int(np.prod(batch))
+
+    def fold(x):
+        if x.shape[:-2] != batch:
+            x = x.broadcast_to(batch + x.shape[-2:])
+        x = _gemm_operand(x, dtype, rt)
+        deferred.flush()
+        return x if len(batch) == 1 else x.reshape((nb,) + x.shape[-2:])
+
+    deferred.flush()
+    a, b = fold(a), fold(b)
+    out_bd = rt.bmm_op(a.bdarray, b.bdarray)
+    out = ndarray(out_bd, View.identity(out_bd.shape))
+    return out if len(batch) == 1 else out.reshape(batch + (m, n))
+
+
+def _matmul_float(a, b, dtype):
+    """The HIP paths of a float32 / float64 matmul; None where the shapes do
+    not fit (the composition then raises the error) or for 1-D · 1-D."""
+    if a.ndim == 0 or b.ndim == 0 or (a.ndim == 1 and b.ndim == 1):
+        return None
+    if a.shape[-1] != b.shape[0 if b.ndim == 1 else -2]:
+        return None
+    if a.ndim == 2 and b.ndim == 2:
+        return _matmul_gemm(a, b, dtype)
+    if a.ndim <= 2 and b.ndim <= 2:
+        return _matmul_gemv(a, b, dtype)
+    # a 1-D operand beside an N-D one is a one-row / one-column matrix
+    # (NumPy's promotion); the added axis is dropped from the result
+    a2 = a.reshape(1, a.shape[0]) if a.ndim == 1 else a
+    b2 = b.reshape(b.shape[0], 1) if b.ndim == 1 else b
+    try:
+        np.broadcast_shapes(a2.shape[:-2], b2.shape[:-2])
+    except ValueError:
+        return None
+    out = _matmul_batched(a2, b2, dtype)
+    if a.ndim == 1:
+        return out.reshape(out.shape[:-2] + out.shape[-1:])
+    if b.ndim == 1:
+        return out.reshape(out.shape[:-1])
+    return out
 
 
 def _matmul_composed(a, b):
@@ -1485,22 +1553,27 @@ def _matmul_composed(a, b):
 
 
 def matmul(a, b):
-    """reference matmul (ramba.py:6953).  2-D @ 2-D with a float32 or
-    float64 result type is a dense GEMM on the matrix units: each rank
-    multiplies its rows of A by row panels of B that travel round a ring
-    (`runtime.matmul_op`, the rt_gemm kernel), with no M·K·N temporary.
-    Every other case (integer and bool operands, 1-D operands, batched
-    N-D) lowers to `_matmul_composed`."""
+    """reference matmul (ramba.py:6953).  With a float32 or float64 result
+    type every form but 1-D · 1-D runs on hand-written kernels and forms no
+    temporary larger than its (broadcast) operands: 2-D @ 2-D is a dense
+    GEMM on the matrix units, each rank multiplying its rows of A by row
+    panels of B that travel round a ring (`runtime.matmul_op`, rt_gemm);
+    2-D @ 1-D and 1-D @ 2-D are a bandwidth-bound GEMV (`matvec_op` /
+    `vecmat_op`, rt_gemv); N-D operands are one batched GEMM per rank over
+    the broadcast, folded batch axes (`bmm_op`, rt_gemm_batched).  Integer
+    and bool operands and 1-D · 1-D (already one fused multiply-sum kernel)
+    lower to `_matmul_composed`."""
     if isinstance(a, np.ndarray):
         a = fromarray(a)
     if isinstance(b, np.ndarray):
         b = fromarray(b)
     if not isinstance(a, ndarray) or not isinstance(b, ndarray):
         raise ValueError("matmul cannot be used with scalar arguments")
-    if a.ndim == 2 and b.ndim == 2 and a.shape[1] == b.shape[0]:
-        dtype = np.result_type(a.dtype, b.dtype)
-        if dtype in (np.float32, np.float64):
-            return _matmul_gemm(a, b, np.dtype(dtype))
+    dtype = np.result_type(a.dtype, b.dtype)
+    if dtype in (np.float32, np.float64):
+        out = _matmul_float(a, b, np.dtype(dtype))
+        if out is not None:
+            return out
     return _matmul_composed(a, b)
 
 

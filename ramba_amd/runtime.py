@@ -1199,6 +1199,113 @@ def matmul_op(self, a_bd, b_bd):
 Runtime.matmul_op = matmul_op
 
 # ---------------------------------------------------------------------------
+# matmul with a 1-D operand, and batched matmul.  Every operand sits on
+# contiguous_divisions (axis 0 only; the frontend repartitions first).
+#
+# matvec_op  y = A @ x.  A and y are split over M, x over K: every rank
+#   assembles all of x in one dense buffer by one pairwise exchange of the
+#   pieces (lengths from x's divisions; at world 1 x is read in place), then
+#   runs one GEMV on its rows.
+# vecmat_op  y = x @ A.  x and A's rows share the split of K, so a rank's
+#   GEMV (on A's transposed strides) gives a length-N partial of all of y; y
+#   is split over N.  Rank j receives its slice of every partial and adds
+#   them in ascending rank order, its own at its place in that order, so the
+#   bits do not depend on arrival order.  Ranks without rows of A send
+#   nothing and are never waited on.
+# bmm_op  C[i] = A[i] @ B[i].  All three are split over the batch axis: one
+#   batched GEMM per rank, no exchange.
+# ---------------------------------------------------------------------------
+
+
+def _on_contiguous(self, who, *bds):
+    for bd in bds:
+        assert bd.constructed and np.array_equal(
+            bd.divisions, contiguous_divisions(self.world, bd.shape)), \
+            f"{who}: operands must sit on contiguous_divisions " \
+            "(frontend repartitions first)"
+
+
+def _span(bd, r):
+    d = bd.divisions[r]
+    return int(d[0, 0]), int(d[1, 0]) + 1            # empty: hi <= lo
+
+
+def matvec_op(self, a_bd, x_bd):
+    from . import gemm as _gemm
+    (M, K), W, me = a_bd.shape, self.world, self.rank
+    assert x_bd.shape == (K,) and a_bd.dtype == x_bd.dtype
+    _on_contiguous(self, "matvec_op", a_bd, x_bd)
+    out_bd = self.new_result((M,), a_bd.dtype, contiguous_divisions(W, (M,)))
+    assert np.array_equal(out_bd.divisions[:, :, 0], a_bd.divisions[:, :, 0])
+    hooks = _gemm.hooks_for(self.backend)
+    x = hooks.gemv_vector(x_bd, self)
+    if W > 1:
+        mine, x = x, self.backend.new_message_buffer((K,), a_bd.dtype)
+        sends = [(r, mine) for r in range(W) if r != me and mine.shape[0]]
+        recvs = []
+        for r in range(W):
+            k0, k1 = _span(x_bd, r)
+            if r == me:
+                x[k0:max(k1, k0)] = mine
+            elif k1 > k0:
+                recvs.append((r, x[k0:k1]))
+        self.backend.exchange(sends, recvs)
+    hooks.gemv_local(out_bd, self, a_bd, x)
+    return out_bd
+
+
+def vecmat_op(self, x_bd, a_bd):
+    from . import gemm as _gemm
+    (K, N), W, me = a_bd.shape, self.world, self.rank
+    assert x_bd.shape == (K,) and a_bd.dtype == x_bd.dtype
+    _on_contiguous(self, "vecmat_op", a_bd, x_bd)
+    assert np.array_equal(x_bd.divisions[:, :, 0], a_bd.divisions[:, :, 0])
+    out_bd = self.new_result((N,), a_bd.dtype, contiguous_divisions(W, (N,)))
+    part = _gemm.hooks_for(self.backend).gemv_t_local(a_bd, self, x_bd)
+    n0, n1 = _span(out_bd, me)
+    sends = []
+    if part is not None:
+        for r in range(W):
+            s0, s1 = _span(out_bd, r)
+            if r != me and s1 > s0:
+                sends.append((r, part[s0:s1]))
+    pieces = []             # (rank, its partial of y[n0:n1]), ranks ascending
+    for r in range(W):
+        k0, k1 = _span(a_bd, r)
+        if k1 > k0 and n1 > n0:
+            pieces.append((r, part[n0:n1] if r == me else
+                           self.backend.new_message_buffer((n1 - n0,),
+                                                           a_bd.dtype)))
+    recvs = [(r, buf) for r, buf in pieces if r != me]
+    if sends or recvs:
+        self.backend.exchange(sends, recvs)
+    core = self.core_box(out_bd, me)
+    for i, (_, buf) in enumerate(pieces):
+        if i == 0:
+            self.backend.unpack_box_to_container(out_bd, self, core, buf)
+        else:
+            self.backend.combine_box_into_container(out_bd, self, core, buf,
+                                                    "sum")
+    return out_bd
+
+
+def bmm_op(self, a_bd, b_bd):
+    from . import gemm as _gemm
+    (B, M, K), (B2, K2, N) = a_bd.shape, b_bd.shape
+    assert (B, K) == (B2, K2) and a_bd.dtype == b_bd.dtype
+    _on_contiguous(self, "bmm_op", a_bd, b_bd)
+    out_bd = self.new_result((B, M, N), a_bd.dtype,
+                             contiguous_divisions(self.world, (B, M, N)))
+    assert np.array_equal(out_bd.divisions[:, :, 0], a_bd.divisions[:, :, 0])
+    _gemm.hooks_for(self.backend).bgemm_local(out_bd, self, a_bd, b_bd)
+    return out_bd
+
+
+Runtime.matvec_op = matvec_op
+Runtime.vecmat_op = vecmat_op
+Runtime.bmm_op = bmm_op
+
+# ---------------------------------------------------------------------------
 # argmax / argmin / nanargmax / nanargmin (the reference lists them as
 # to-do, ramba/ramba.py:10288).  A (value, index) pair is carried through
 # the local kernel tree and the cross-rank combine.  Every rank reports

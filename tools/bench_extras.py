@@ -332,8 +332,124 @@ def gemm_leg(repeats=5, sizes=(1024, 4096)):
             ra.sync()
 
 
+HBM_PEAK = 8e12    # AMD Instinct MI355X data sheet, bytes/s
+
+
+def _forms_leg(tag, cases, repeats=5):
+    """Shared method of the gemv / bgemm legs, that of gemm_leg: every shape
+    warmed, host clock around `inner` calls ending in a synchronise,
+    `repeats` windows per variant, the variants alternating in one process.
+    A case is (name, dtype, make -> (a, b, torch fn, work, peak)): `work` is
+    the bytes of A (gemv) or the FLOPs (bgemm), `peak` its data-sheet peak.
+    The composition runs only where it can hold the shape; there the public
+    path's slowest window must be under the composition's fastest."""
+    import torch
+    from ramba_amd import deferred
+    from ramba_amd.ndarray import _matmul_composed
+    rt = deferred.get_runtime()
+    be = rt.backend
+
+    def core(arr):
+        bd = arr.bdarray
+        _, _, _, pads = rt.shard_geometry(bd)
+        sl = tuple(slice(p, p + s) for p, s in zip(pads, bd.shape))
+        return be._cont(bd)[sl]
+
+    def window(fn, inner):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(inner):
+            r = fn()
+        ra.sync()
+        torch.cuda.synchronize()
+        del r
+        return (time.perf_counter() - t0) / inner * 1e3
+
+    for name, dt, shapes, tfn, work, peak, composed in cases:
+        a, b = (ra.fromfunction(
+            (lambda *i: ((sum((3 + 4 * d) * x for d, x in enumerate(i))
+                          + 7 * q) % 1000) * 1e-3 - 0.5),
+            shp, dtype=np.dtype(dt)) for q, shp in enumerate(shapes))
+        ra.sync()
+        ta, tb = core(a), core(b)
+        impls = {"a @ b": (lambda: a @ b, 10),
+                 "torch": (lambda: tfn(ta, tb), 10)}
+        if composed:
+            impls["composition"] = (lambda: _matmul_composed(a, b), 3)
+        for fn, _ in impls.values():
+            fn()
+        ra.sync()
+        c = a @ b
+        ra.sync()
+        tol = 1e-3 if dt == "float32" else 1e-10
+        assert torch.allclose(core(c), tfn(ta, tb), rtol=tol, atol=tol), name
+        del c
+        times = {k: [] for k in impls}
+        for _ in range(repeats):
+            for k, (fn, inner) in impls.items():
+                times[k].append(window(fn, inner))
+        rec = {"case": f"{tag}_{name}_{dt}", "work": work, "peak": peak,
+               "repeats": repeats}
+        for k, ts in times.items():
+            ts = sorted(ts)
+            med = ts[len(ts) // 2]
+            rec[k] = {"ms_median": round(med, 4), "ms_min": round(ts[0], 4),
+                      "ms_max": round(ts[-1], 4),
+                      "rate_median": round(work / (med * 1e-3), 1),
+                      "share_of_peak": round(work / (med * 1e-3) / peak, 4)}
+        rec["torch_over_ours"] = round(
+            rec["torch"]["ms_median"] / rec["a @ b"]["ms_median"], 3)
+        if composed:
+            rec["composition_over_ours"] = round(
+                rec["composition"]["ms_median"] / rec["a @ b"]["ms_median"], 1)
+            rec["beats_composition_beyond_spread"] = \
+                rec["a @ b"]["ms_max"] < rec["composition"]["ms_min"]
+        print(tag.upper() + " " + json.dumps(rec), flush=True)
+        del a, b, ta, tb
+        ra.sync()
+
+
+def gemv_leg(n=16384):
+    """A @ x and x @ A: bytes/s of A traffic against the HBM peak.  Besides
+    n^2 in both dtypes, a few-rows / long-K case for each kernel family,
+    where the K-split fills the chip."""
+    import torch
+    mv = lambda ta, tb: torch.mv(ta, tb)
+    vm = lambda ta, tb: torch.mv(tb.t(), ta)
+    cases = []
+    for dt in ("float32", "float64"):
+        isz = np.dtype(dt).itemsize
+        cases += [(f"Ax_{n}^2", dt, ((n, n), (n,)), mv, n * n * isz,
+                   HBM_PEAK, n <= 16384),
+                  (f"xA_{n}^2", dt, ((n,), (n, n)), vm, n * n * isz,
+                   HBM_PEAK, n <= 16384)]
+    cases += [("Ax_64x4194304", "float32", ((64, 1 << 22), (1 << 22,)), mv,
+               64 * (1 << 22) * 4, HBM_PEAK, True),
+              ("xA_4194304x64", "float32", ((1 << 22,), (1 << 22, 64)), vm,
+               64 * (1 << 22) * 4, HBM_PEAK, True)]
+    _forms_leg("gemv", cases)
+
+
+def bgemm_leg():
+    """Batched matmul: FLOP/s against the matrix peak, at 64 x 512^3 (the
+    composition cannot hold it) and at many small matrices, 4096 x 32^3,
+    where most of each 128 x 128 tile is wasted."""
+    import torch
+    cases = []
+    for dt in ("float32", "float64"):
+        for b, n, composed in ((64, 512, False), (4096, 32, True)):
+            cases.append((f"{b}x{n}^3", dt, ((b, n, n), (b, n, n)),
+                          torch.bmm, 2.0 * b * n ** 3, MATRIX_PEAK[dt],
+                          composed))
+    _forms_leg("bgemm", cases)
+
+
 def main():
     ra.init()
+    if sys.argv[1:] in (["gemv"], ["bgemm"]):
+        {"gemv": gemv_leg, "bgemm": bgemm_leg}[sys.argv[1]]()
+        print("done", flush=True)
+        return
     if sys.argv[1:2] == ["gemm"]:
         # optional sizes for a quick look: gemm N [N ...]
         sizes = [int(x) for x in sys.argv[2:]]
@@ -378,6 +494,8 @@ def main():
     take_leg()
     argreduce_leg()
     gemm_leg()
+    gemv_leg()
+    bgemm_leg()
     print("done", flush=True)
 
 
