@@ -23,6 +23,7 @@
  *                       (ramba.py:3056, 6953-7040), on the MFMA units
  *   rt_gemm_batched   — the same for N-D (batched) operands
  *   rt_gemv           — the same for one 1-D operand (A @ x, x @ A)
+ *   rt_hist           — histogram / bincount (no reference counterpart)
  *   rt_stream_sync /
  *   rt_device_sync    — worker-side completion (sync, ramba.py:9843)
  *   rt_event_*        — hot-loop timing (add_time, ramba.py:945-1022)
@@ -77,7 +78,7 @@ int rt_launch(void *kernel, unsigned gx, unsigned gy, unsigned gz,
               size_t argsize);
 
 /* Argument contract shared by rt_copy_box, rt_combine_box, rt_cumsum,
- * rt_mask_compact, rt_axis_scan and rt_flat_copy (the contract of
+ * rt_mask_compact, rt_axis_scan, rt_flat_copy and rt_hist (the contract of
  * rt_take_rows): every argument is checked on the host before any HIP call
  * and a bad one returns nonzero with rt_last_error() naming the entry point
  * and the argument.  Rejected: nd out of range; NULL shape / strides; a
@@ -318,6 +319,53 @@ int rt_gemv_geometry(int dtype, int regime, int *rows_per_block, int *k_step);
 int rt_gemv_plan(const void *a, int64_t M, int64_t K, int64_t a_rs,
                  int64_t a_cs, int dtype, int cus, int *regime,
                  int64_t *ksplit);
+
+/* histogram / bincount — a keyed count (numpy.histogram, numpy.bincount; the
+ * reference has neither).  One pass over a strided box of 1..4 axes at
+ * `in + in_off` (offset and strides in elements, any sign, zero allowed),
+ * binned as if flattened; the kernel ADDS into counts, a device
+ * int64[nbins] that the caller zeroes.  dtype: any rt_dtype.
+ * mode:
+ *   0 INDEX    integer dtypes and RT_U8: the bin is the value; values < 0 or
+ *              >= nbins are skipped and counted in *bad (device uint32, may
+ *              be NULL).  Nothing outside counts is ever written.
+ *   1 UNIFORM  edges: device array of nbins + 1 values, edges_dtype RT_F32
+ *              or RT_F64.  NumPy's index computation in that dtype: drop x
+ *              unless first <= x <= last (NaN fails); convert x; f = ((x -
+ *              first) / (last - first)) * nbins with one IEEE divide and one
+ *              IEEE multiply; truncate; nbins becomes nbins - 1; one step
+ *              down if x < edges[i], else one up if x >= edges[i+1] and i is
+ *              not the last bin.
+ *   2 EDGES    any non-decreasing edges, RT_F64: x goes to bin i iff
+ *              edges[i] <= x < edges[i+1] (last bin closed), by binary
+ *              search, compared in float64; NaN and values outside are
+ *              dropped.
+ * Range tests and the EDGES search compare in float64, so int64 values above
+ * 2^53 are binned by their rounded value.  Edge lists of at most
+ * edges_lds_max values are staged in LDS, longer ones are read in place.
+ * Counters by nbins (rt_hist_regime): 0 LDS_WAVE, nbins <= wave_max_bins, a
+ * private uint32 LDS copy per wave of the 256-lane block; 1 LDS_BLOCK,
+ * nbins <= block_max_bins, one uint32 LDS copy per block; 2 GLOBAL, 64-bit
+ * atomic adds on counts.  A block adds its nonzero LDS bins to counts with
+ * 64-bit atomic adds (integers: the counts do not depend on the order); at
+ * most grid_cap blocks run, and no block counts more than 2^31 elements
+ * between flushes.  Only when every active lane of a wave holds the same bin
+ * does one lane add the lane count; any other mix adds lane by lane.
+ * 16-byte loads under the rt_arg_flat_regime rule, else element loads.
+ * Validated before any HIP call (the contract above): nd, NULL shape /
+ * strides, extents, dtype, mode, INDEX with a float dtype, nbins < 1 or
+ * >= 2^40, NULL edges or a bad edges_dtype in modes 1 and 2, NULL in /
+ * counts with work to do.  A zero extent returns 0 without launching.
+ * rt_hist_regime: the regime for nbins, -1 if nbins is invalid.
+ * rt_hist_geometry: the compiled-in constants (any pointer may be NULL).
+ * Both are host arithmetic only. */
+int rt_hist(uintptr_t stream, const void *in, int64_t in_off, int nd,
+            const int64_t *shape, const int64_t *strides, int dtype, int mode,
+            const void *edges, int edges_dtype, int64_t nbins, void *counts,
+            void *bad);
+int rt_hist_regime(int64_t nbins);
+int rt_hist_geometry(int *grid_cap, int *block, int64_t *wave_max_bins,
+                     int64_t *block_max_bins, int64_t *edges_lds_max);
 
 int rt_stream_sync(uintptr_t stream);
 int rt_device_sync(void);

@@ -3053,3 +3053,414 @@ extern "C" int rt_gemv(uintptr_t stream, void *y, const void *a,
                                    nparts);
     return gemv_launch<float>(stream, y, a, x, scratch, g, regime, nparts);
 }
+
+// ---------------------------------------------------------------------------
+// Histogram / bincount: a keyed count.  One pass over a strided box (the
+// rt_arg_flat addressing and load rule), every element mapped to a bin and
+// counted; `counts` (int64[nbins], zeroed by the caller) is added to.
+//
+// Binning modes
+//   INDEX    the bin is the (integer) value; values outside [0, nbins) are
+//            skipped and counted in *bad.
+//   UNIFORM  numpy.lib._histograms_impl restated in the edges' dtype E: drop
+//            x unless first <= x <= last (NaN fails), f = ((x - first) /
+//            (last - first)) * nbins with one IEEE divide and one IEEE
+//            multiply, truncate, nbins -> nbins - 1, then step down if
+//            x < edges[i], else up if x >= edges[i + 1] and i is not the
+//            last bin.  The correction makes the bin a function of the edges
+//            alone as long as the guess is within one bin of the truth.
+//   EDGES    any non-decreasing float64 edges: binary search for the number
+//            of edges <= x, compared in float64; the last bin is closed;
+//            NaN and values outside [first, last] are dropped.
+// Edges of at most HIST_EDGES_LDS_MAX values are staged in LDS; longer lists
+// are read where they are (they stay in L2).
+//
+// Counters, by nbins (rt_hist_regime):
+//   LDS_WAVE   nbins <= HIST_WAVE_MAX_BINS: each of the block's four waves
+//              adds into its own uint32 LDS copy, so a hot bin is contended
+//              by 64 lanes, not 256; the copies are summed at the flush.
+//              4 x 2048 x 4 B = 32 KB keeps five blocks on a CU.
+//   LDS_BLOCK  nbins <= HIST_BLOCK_MAX_BINS: one uint32 LDS copy per block.
+//              32768 bins are 128 KB, the largest power of two inside the
+//              160 KB of a gfx950 CU and the most LDS the kernel ever asks
+//              for: edges are staged only below HIST_EDGES_LDS_MAX values,
+//              where the counters are small.
+//   GLOBAL     64-bit atomic adds straight on counts.
+// A block flushes only its nonzero LDS bins, with 64-bit global atomic adds
+// (integer adds: any order gives the same counts).  The grid is capped at
+// HIST_GRID_CAP blocks, so the flush is at most grid x nbins adds.  A launch
+// covers at most HIST_LAUNCH_TRIPS load units per lane, i.e. at most 2^31
+// elements per block, so a uint32 LDS counter cannot wrap; longer boxes take
+// several launches.
+//
+// Wave pre-aggregation: when every active lane of a wave holds the same bin
+// (sorted or constant data), one lane adds the lane count; any other mix of
+// bins adds lane by lane.  The test is two readfirstlanes and a ballot per
+// element.  -DHIST_PREAGG=0 builds the kernel without it, to measure it
+// (tools/bench_hist.py --lib).
+// ---------------------------------------------------------------------------
+
+#ifndef HIST_PREAGG
+#define HIST_PREAGG 1
+#endif
+
+namespace {
+
+enum { HIST_INDEX = 0, HIST_UNIFORM = 1, HIST_EDGES = 2 };
+enum { HIST_LDS_WAVE = 0, HIST_LDS_BLOCK = 1, HIST_GLOBAL = 2 };
+enum {
+    HIST_GRID_CAP = 2048,          // 256 CUs x 8 blocks, as ARG_GRID_CAP
+    HIST_WAVE_MAX_BINS = 2048,
+    HIST_BLOCK_MAX_BINS = 32768,
+    HIST_EDGES_LDS_MAX = 4096,     // edge values (32 KB of float64)
+    HIST_LAUNCH_TRIPS = 1 << 19    // x 256 lanes x 16 elements = 2^31
+};
+
+struct HistArgs {
+    int64_t u0, u1;          // this launch's load units [u0, u1)
+    int64_t shp[4];          // extents, right-aligned; innermost in units
+    int64_t str[4];          // strides in load units
+    int64_t tail0, tailn;    // 1-D 16-byte path: elements past the last unit
+    int64_t nbins;
+    int nd, regime, stage_edges;
+};
+
+int hist_regime(int64_t nbins) {
+    return nbins <= HIST_WAVE_MAX_BINS    ? HIST_LDS_WAVE
+           : nbins <= HIST_BLOCK_MAX_BINS ? HIST_LDS_BLOCK
+                                          : HIST_GLOBAL;
+}
+
+__device__ __forceinline__ int64_t hist_unit_off(const HistArgs &a,
+                                                 int64_t u) {
+    if (a.nd == 1) return u * a.str[3];
+    uint64_t rem = (uint64_t)u;
+    int64_t off = 0;
+#pragma unroll
+    for (int d = 3; d >= 0; --d) {
+        if (d < 4 - a.nd) break;      // the axes the host left after merging
+        const uint64_t q = rem / (uint64_t)a.shp[d];
+        off += (int64_t)(rem - q * (uint64_t)a.shp[d]) * a.str[d];
+        rem = q;
+    }
+    return off;
+}
+
+// Where a lane's counts go: its wave's (or block's) LDS copy, or counts.
+struct HistSink {
+    uint32_t *lds;                 // nullptr in the GLOBAL regime
+    unsigned long long *counts;
+    int64_t nbins;
+
+    __device__ __forceinline__ void add(int64_t b, uint32_t k) const {
+        if (lds)
+            atomicAdd(&lds[b], k);
+        else
+            atomicAdd(&counts[b], (unsigned long long)k);
+    }
+
+    // b < 0: nothing to count.  Anything else is inside [0, nbins).  When
+    // every active lane holds the same bin, the first one adds them all.
+    __device__ __forceinline__ void count(int64_t b) const {
+        if (HIST_PREAGG) {
+            const uint64_t act = __ballot(1);
+            const int64_t b0 = gemm_uniform(b);
+            if (__ballot(b == b0) == act) {
+                if (b0 >= 0
+                    && (int)__lane_id() == __ffsll((long long)act) - 1)
+                    add(b0, (uint32_t)__popcll(act));
+                return;
+            }
+        }
+        if (b >= 0) add(b, 1u);
+    }
+};
+
+template <typename T>
+__device__ __forceinline__ int64_t hist_bin_index(T x, int64_t nbins) {
+    const int64_t v = (int64_t)x;
+    return (uint64_t)v < (uint64_t)nbins ? v : -1;
+}
+
+template <typename T, typename E>
+__device__ __forceinline__ int64_t hist_bin_uniform(T x, const E *edges,
+                                                    int64_t nbins, E first,
+                                                    E last) {
+#pragma clang fp contract(off)
+    const double xd = (double)x;
+    if (!(xd >= (double)first && xd <= (double)last)) return -1;
+    const E xe = (E)x;
+    E f;
+    if constexpr (sizeof(E) == 4)
+        f = __fmul_rn(__fdiv_rn(xe - first, last - first), (E)nbins);
+    else
+        f = __dmul_rn(__ddiv_rn(xe - first, last - first), (E)nbins);
+    int64_t i = (int64_t)f;
+    if (i == nbins) i = nbins - 1;
+    if ((uint64_t)i >= (uint64_t)nbins) return -1;   // keeps the reads inside
+    if (xe < edges[i])
+        --i;
+    else if (xe >= edges[i + 1] && i != nbins - 1)
+        ++i;
+    return (uint64_t)i < (uint64_t)nbins ? i : -1;
+}
+
+template <typename T>
+__device__ __forceinline__ int64_t hist_bin_edges(T x, const double *edges,
+                                                  int64_t nbins, double first,
+                                                  double last) {
+    const double xd = (double)x;
+    if (!(xd >= first && xd <= last)) return -1;
+    // lo = number of edges <= x (>= 1 here); edges[nbins] == x gives
+    // nbins + 1, the closed last bin
+    int64_t lo = 1, hi = nbins + 1;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (edges[mid] <= xd)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return lo > nbins ? nbins - 1 : lo - 1;
+}
+
+template <typename T, typename L, typename E, int MODE>
+__device__ __forceinline__ void hist_unit(const L &unit, const HistSink &sink,
+                                          const E *edges, E first, E last,
+                                          uint32_t &nbad) {
+    constexpr int PER = sizeof(L) / sizeof(T);
+    T e[PER];
+    __builtin_memcpy(e, &unit, sizeof(L));
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+        int64_t b;
+        if constexpr (MODE == HIST_INDEX) {
+            b = hist_bin_index<T>(e[j], sink.nbins);
+            nbad += b < 0;
+        } else if constexpr (MODE == HIST_UNIFORM) {
+            b = hist_bin_uniform<T, E>(e[j], edges, sink.nbins, first, last);
+        } else {
+            b = hist_bin_edges<T>(e[j], edges, sink.nbins, first, last);
+        }
+        sink.count(b);
+    }
+}
+
+// LDS layout: [staged edges, E x (nbins + 1)] [counters, uint32 x copies x
+// nbins]; either part may be absent.  L = uint4 when the box takes 16-byte
+// loads, else one element; two loads in flight per lane.
+template <typename T, typename L, typename E, int MODE>
+__global__ __launch_bounds__(256) GEMM_NO_PK_F32 void hist_kernel(
+    const T *__restrict__ in, HistArgs a, const E *__restrict__ edges,
+    unsigned long long *__restrict__ counts, unsigned int *__restrict__ bad) {
+    extern __shared__ __align__(16) unsigned char hist_lds[];
+    const int tid = threadIdx.x;
+    const int64_t nbins = a.nbins;
+    E first = E(0), last = E(0);
+    uint32_t *cnt = reinterpret_cast<uint32_t *>(hist_lds);
+    if constexpr (MODE != HIST_INDEX) {
+        first = edges[0];
+        last = edges[nbins];
+        if (a.stage_edges) {
+            E *se = reinterpret_cast<E *>(hist_lds);
+            for (int64_t k = tid; k <= nbins; k += 256) se[k] = edges[k];
+            // counters start on the next 8-byte boundary
+            cnt = reinterpret_cast<uint32_t *>(
+                hist_lds + (((nbins + 1) * sizeof(E) + 7) & ~(size_t)7));
+            edges = se;
+        }
+    }
+    const int copies = a.regime == HIST_LDS_WAVE    ? 4
+                       : a.regime == HIST_LDS_BLOCK ? 1
+                                                    : 0;
+    for (int64_t k = tid; k < copies * nbins; k += 256) cnt[k] = 0u;
+    __syncthreads();
+
+    HistSink sink;
+    sink.lds = copies == 0   ? nullptr
+               : copies == 4 ? cnt + (tid >> 6) * nbins
+                             : cnt;
+    sink.counts = counts;
+    sink.nbins = nbins;
+    uint32_t nbad = 0;
+
+    const L *src = reinterpret_cast<const L *>(in);
+    const int64_t S = (int64_t)gridDim.x * 256;
+    int64_t u = a.u0 + (int64_t)blockIdx.x * 256 + tid;
+    for (; u + S < a.u1; u += 2 * S) {
+        const L x0 = src[hist_unit_off(a, u)];
+        const L x1 = src[hist_unit_off(a, u + S)];
+        hist_unit<T, L, E, MODE>(x0, sink, edges, first, last, nbad);
+        hist_unit<T, L, E, MODE>(x1, sink, edges, first, last, nbad);
+    }
+    if (u < a.u1) {
+        const L x0 = src[hist_unit_off(a, u)];
+        hist_unit<T, L, E, MODE>(x0, sink, edges, first, last, nbad);
+    }
+    const int64_t t = (int64_t)blockIdx.x * 256 + tid;
+    if (a.u0 == 0 && t < a.tailn)
+        hist_unit<T, T, E, MODE>(in[a.tail0 + t], sink, edges, first, last,
+                                 nbad);
+    if (MODE == HIST_INDEX && nbad && bad) atomicAdd(bad, nbad);
+
+    if (copies) {
+        __syncthreads();
+        for (int64_t b = tid; b < nbins; b += 256) {
+            uint32_t v = 0;
+            for (int c = 0; c < copies; ++c) v += cnt[c * nbins + b];
+            if (v) atomicAdd(&counts[b], (unsigned long long)v);
+        }
+    }
+}
+
+size_t hist_lds_bytes(int64_t nbins, int regime, bool stage, int edge_size) {
+    const size_t e = stage ? ((size_t)(nbins + 1) * edge_size + 7) & ~(size_t)7
+                           : 0;
+    const size_t copies = regime == HIST_LDS_WAVE    ? 4
+                          : regime == HIST_LDS_BLOCK ? 1
+                                                     : 0;
+    return e + copies * (size_t)nbins * sizeof(uint32_t);
+}
+
+template <typename T, typename L, typename E, int MODE>
+int hist_launch_k(uintptr_t stream, const T *src, HistArgs a, int64_t nunits,
+                  const void *edges, void *counts, void *bad) {
+    auto kern = hist_kernel<T, L, E, MODE>;
+    const size_t lds = hist_lds_bytes(a.nbins, a.regime, a.stage_edges != 0,
+                                      sizeof(E));
+    // beyond 64 KB a kernel has to be granted its LDS: once per
+    // instantiation, for the most it can ask (the top of LDS_BLOCK)
+    if (lds > 64 * 1024) {
+        static const hipError_t granted = hipFuncSetAttribute(
+            reinterpret_cast<const void *>(kern),
+            hipFuncAttributeMaxDynamicSharedMemorySize,
+            HIST_BLOCK_MAX_BINS * (int)sizeof(uint32_t));
+        HIP_CHECK(granted);
+    }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    // a launch covers at most HIST_LAUNCH_TRIPS units per lane of the capped
+    // grid; the 1-D scalar tail rides on the first one (also when nunits = 0)
+    const int64_t span = (int64_t)HIST_GRID_CAP * 256 * HIST_LAUNCH_TRIPS;
+    for (int64_t u0 = 0; u0 == 0 || u0 < nunits; u0 += span) {
+        a.u0 = u0;
+        a.u1 = nunits - u0 < span ? nunits : u0 + span;
+        int64_t blocks = (a.u1 - a.u0 + 255) / 256;
+        if (blocks > HIST_GRID_CAP) blocks = HIST_GRID_CAP;
+        if (blocks < 1) blocks = 1;
+        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds, st,
+                           src, a, static_cast<const E *>(edges),
+                           static_cast<unsigned long long *>(counts),
+                           static_cast<unsigned int *>(bad));
+        if (launched("rt_hist")) return 1;
+    }
+    return 0;
+}
+
+template <typename T, typename L>
+int hist_launch_l(uintptr_t stream, const T *src, const HistArgs &a,
+                  int64_t nunits, int mode, const void *edges,
+                  int edges_dtype, void *counts, void *bad) {
+    if (mode == HIST_INDEX) {
+        if constexpr (std::is_integral<T>::value)
+            return hist_launch_k<T, L, double, HIST_INDEX>(
+                stream, src, a, nunits, nullptr, counts, bad);
+        return fail("rt_hist", "INDEX mode needs an integer dtype");
+    }
+    if (mode == HIST_EDGES)
+        return hist_launch_k<T, L, double, HIST_EDGES>(stream, src, a, nunits,
+                                                       edges, counts, bad);
+    if (edges_dtype == RT_F32)
+        return hist_launch_k<T, L, float, HIST_UNIFORM>(stream, src, a, nunits,
+                                                        edges, counts, bad);
+    return hist_launch_k<T, L, double, HIST_UNIFORM>(stream, src, a, nunits,
+                                                     edges, counts, bad);
+}
+
+}  // namespace
+
+extern "C" int rt_hist_regime(int64_t nbins) {
+    if (nbins < 1 || nbins >= (1LL << 40)) return -1;
+    return hist_regime(nbins);
+}
+
+extern "C" int rt_hist_geometry(int *grid_cap, int *block,
+                                int64_t *wave_max_bins,
+                                int64_t *block_max_bins,
+                                int64_t *edges_lds_max) {
+    if (grid_cap) *grid_cap = HIST_GRID_CAP;
+    if (block) *block = 256;
+    if (wave_max_bins) *wave_max_bins = HIST_WAVE_MAX_BINS;
+    if (block_max_bins) *block_max_bins = HIST_BLOCK_MAX_BINS;
+    if (edges_lds_max) *edges_lds_max = HIST_EDGES_LDS_MAX;
+    return 0;
+}
+
+extern "C" int rt_hist(uintptr_t stream, const void *in, int64_t in_off,
+                       int nd, const int64_t *shape, const int64_t *strides,
+                       int dtype, int mode, const void *edges,
+                       int edges_dtype, int64_t nbins, void *counts,
+                       void *bad) {
+    const char *who = "rt_hist";
+    int64_t n;
+    if (box_extents(who, nd, 1, shape, strides, strides, &n)) return 1;
+    if (dtype < RT_F64 || dtype > RT_U8) return fail(who, "bad dtype");
+    if (mode < HIST_INDEX || mode > HIST_EDGES) return fail(who, "bad mode");
+    if (mode == HIST_INDEX && (dtype == RT_F64 || dtype == RT_F32))
+        return fail(who, "INDEX mode needs an integer dtype");
+    if (nbins < 1) return fail(who, "nbins < 1");
+    if (nbins >= (1LL << 40)) return fail(who, "nbins out of range");
+    if (mode != HIST_INDEX) {
+        if (!edges) return fail(who, "NULL edges");
+        if (edges_dtype != RT_F64 && !(mode == HIST_UNIFORM
+                                       && edges_dtype == RT_F32))
+            return fail(who, "bad edges dtype");
+    }
+    if (n == 0) return 0;
+    if (!in) return fail(who, "NULL in");
+    if (!counts) return fail(who, "NULL counts");
+
+    return dtype_dispatch<7>(who, dtype, [&](auto t) {
+        using T = decltype(t);
+        const bool vec =
+            arg_flat_vec(in, in_off, nd, shape, strides, sizeof(T));
+        const int64_t per = vec ? 16 / (int64_t)sizeof(T) : 1;
+        HistArgs a;
+        a.nd = nd;
+        a.nbins = nbins;
+        a.regime = hist_regime(nbins);
+        a.stage_edges = mode != HIST_INDEX && nbins + 1 <= HIST_EDGES_LDS_MAX;
+        a.tail0 = a.tailn = 0;
+        for (int d = 0; d < 4; ++d) {
+            const int s = d - (4 - nd);
+            a.shp[d] = s >= 0 ? shape[s] : 1;
+            a.str[d] = s >= 0 ? strides[s] : 0;
+            if (vec && d < 3) a.str[d] /= per;
+        }
+        int64_t nunits = n;
+        if (vec) {
+            a.tail0 = (a.shp[3] / per) * per;
+            a.tailn = a.shp[3] - a.tail0;     // nonzero only when nd == 1
+            a.shp[3] /= per;
+            nunits = n / shape[nd - 1] * a.shp[3];
+        }
+        // merge every axis that is dense over its inner neighbour, so a
+        // contiguous N-D box walks as one axis, with no division per unit
+        int k = 3;
+        for (int d = 2; d >= 4 - nd; --d) {
+            if (a.str[d] == a.shp[k] * a.str[k]) {
+                a.shp[k] *= a.shp[d];
+            } else {
+                --k;
+                a.shp[k] = a.shp[d];
+                a.str[k] = a.str[d];
+            }
+        }
+        a.nd = 4 - k;
+        const T *src = static_cast<const T *>(in) + in_off;
+        if (vec)
+            return hist_launch_l<T, uint4>(stream, src, a, nunits, mode, edges,
+                                           edges_dtype, counts, bad);
+        return hist_launch_l<T, T>(stream, src, a, nunits, mode, edges,
+                                   edges_dtype, counts, bad);
+    });
+}

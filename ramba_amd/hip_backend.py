@@ -92,6 +92,11 @@ _RT_ABI = {
                                 ctypes.POINTER(_int)]),
     "rt_gemv_plan": (_int, [_vp, _i64, _i64, _i64, _i64, _int, _int,
                             ctypes.POINTER(_int), _p64]),
+    "rt_hist": (_int, [_sz, _vp, _i64, _int, _p64, _p64, _int, _int, _vp,
+                       _int, _i64, _vp, _vp]),
+    "rt_hist_regime": (_int, [_i64]),
+    "rt_hist_geometry": (_int, [ctypes.POINTER(_int), ctypes.POINTER(_int),
+                                _p64, _p64, _p64]),
     "rt_stream_sync": (_int, [_sz]),
     "rt_device_sync": (_int, []),
     "rt_event_create": (_int, [_pvp]),
@@ -121,6 +126,18 @@ def _load_lib():
 
 def _i64arr(vals):
     return (ctypes.c_int64 * len(vals))(*[int(v) for v in vals])
+
+
+def hist_geometry(lib):
+    """rt_hist_geometry as a dict (host arithmetic; needs no GPU)."""
+    cap, blk = ctypes.c_int(), ctypes.c_int()
+    wmax, bmax, emax = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+    lib.rt_hist_geometry(ctypes.byref(cap), ctypes.byref(blk),
+                         ctypes.byref(wmax), ctypes.byref(bmax),
+                         ctypes.byref(emax))
+    return {"grid_cap": cap.value, "block": blk.value,
+            "wave_max_bins": wmax.value, "block_max_bins": bmax.value,
+            "edges_lds_max": emax.value}
 
 
 def _hb_arg_chunks(nd, axis, nout, K):
@@ -1136,6 +1153,40 @@ class HipBackend:
             raise TypeError(
                 f"arg reduction: unsupported value dtype {t.dtype}")
         return code
+
+    # -- histogram / bincount (runtime.hist_op) -------------------------------
+    #
+    # The hook of ramba_amd/histogram.py on rt_hist.  The operand is read in
+    # place through the view's strides; the counts stay on the device.
+
+    hist_dtypes = frozenset(RT_DTYPE)   # hist_op refuses any other, by name
+
+    def hist_geometry(self):
+        """The compiled-in constants of rt_hist, by name."""
+        return hist_geometry(self.lib)
+
+    def hist_partial(self, bd, rt, view, lb, mode, edges, nbins):
+        d_, _, cstrides, pads = rt.shard_geometry(bd)
+        off0, strides = view.operand_addressing(lb[0], cstrides, d_[0], pads)
+        shape = box_shape(lb)
+        cont = self._cont(bd)
+        counts = self.torch.zeros(nbins, dtype=self.torch.int64,
+                                  device="cuda")
+        bad = self.torch.zeros(1, dtype=self.torch.int32, device="cuda")
+        dev_edges, edt = None, 0
+        if edges is not None:
+            edt = RT_DTYPE[str(edges.dtype)]
+            dev_edges = self.torch.from_numpy(
+                np.ascontiguousarray(edges)).to("cuda")
+        self._check(self.lib.rt_hist(
+            self._stream(), ctypes.c_void_p(cont.data_ptr()), int(off0),
+            len(shape), _i64arr(shape), _i64arr(strides),
+            RT_DTYPE[str(np.dtype(bd.dtype))], int(mode),
+            ctypes.c_void_p(dev_edges.data_ptr())
+            if dev_edges is not None else None,
+            edt, int(nbins), ctypes.c_void_p(counts.data_ptr()),
+            ctypes.c_void_p(bad.data_ptr())), "rt_hist")
+        return counts, bad
 
     # -- cross-stage fusion (staged/tiled kernel; ramba_amd/staged.py) --------
 

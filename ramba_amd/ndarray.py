@@ -8,10 +8,12 @@ elementwise / reduction op records IR into the current fused group via
 """
 
 import numbers
+import operator
 
 import numpy as np
 
 from . import deferred, ir
+from . import histogram as _hg   # the submodule; the package's `histogram` is the function below
 from .common import (contiguous_divisions, default_border,
                      default_divisions)
 from .shardview import View, exec_boxes, spans_trailing_axes
@@ -1369,6 +1371,128 @@ nanargmin = _module_arg_reduction("nanargmin")
 ndarray._ARRAY_FUNC.update({
     "argmax": argmax, "argmin": argmin,
     "nanargmax": nanargmax, "nanargmin": nanargmin,
+})
+
+
+# -- histogram / bincount: keyed counts on runtime.hist_op.  NumPy's own
+#    functions, called on an empty array, decide the edges and raise its
+#    errors; only the counting is distributed.  Sync points, like take. -----
+
+def _hist_min_max(a):
+    """(min, max) of a non-empty array as scalars of its dtype (bool as
+    uint8), the same on every rank."""
+    if a.dtype == np.bool_:         # min / max of bools are all / any
+        return np.uint8(a.all()), np.uint8(a.any())
+    return a.dtype.type(a.min()), a.dtype.type(a.max())
+
+
+def _hist_counts(a, mode, edges, nbins):
+    if a.size == 0 or nbins == 0:
+        return zeros(nbins, dtype=np.int64)
+    deferred.flush()
+    out_bd = deferred.get_runtime().hist_op(a, mode, edges, nbins)
+    return ndarray(out_bd, View.identity((nbins,)))
+
+
+def histogram(a, bins=10, range=None, density=None, weights=None):
+    """numpy.histogram for ramba arrays: (hist, bin_edges), `hist` a ramba
+    array and `bin_edges` a host NumPy array with NumPy's dtype and values.
+    weights=, string `bins` and complex input are not supported."""
+    if not isinstance(a, ndarray) and not isinstance(bins, ndarray):
+        return np.histogram(a, bins=bins, range=range, density=density,
+                            weights=weights)
+    if weights is not None:
+        raise NotImplementedError(
+            "histogram: weights= is not supported (a float scatter-add with "
+            "a fixed summation order is a different kernel)")
+    if isinstance(bins, str):
+        raise NotImplementedError(
+            f"histogram: bins={bins!r} (an estimator name) is not supported; "
+            "pass a bin count or the edges")
+    if not isinstance(a, ndarray):
+        a = fromarray(np.asarray(a))
+    if a.dtype.kind == "c":
+        raise NotImplementedError("histogram: complex input is not supported")
+    if a.ndim > 4:
+        raise NotImplementedError(
+            "histogram supports arrays of up to 4 dimensions")
+    if isinstance(bins, ndarray):
+        bins = bins.asarray()
+    empty = np.empty(0, dtype=np.uint8 if a.dtype == np.bool_ else a.dtype)
+    if np.ndim(bins) == 0:
+        mode = _hg.UNIFORM
+        if range is None and a.size:
+            np.histogram_bin_edges(empty, bins)     # a bad `bins` raises now
+            range = _hist_min_max(a)
+            if not (np.isfinite(range[0]) and np.isfinite(range[1])):
+                raise ValueError("autodetected range of [{}, {}] is not "
+                                 "finite".format(*range))
+        bin_edges = np.histogram_bin_edges(empty, bins, range)
+        edges = bin_edges
+    else:
+        mode = _hg.EDGES
+        bin_edges = np.histogram_bin_edges(empty, bins, range)
+        edges = bin_edges.astype(np.float64)
+        if bin_edges.dtype.kind in "iu" and a.dtype == np.int64 and a.size:
+            # int64 against integer edges is an exact comparison in NumPy;
+            # the kernel compares in float64
+            lim = 2 ** 53
+            if max(abs(int(v)) for v in _hist_min_max(a)) > lim or (
+                    bin_edges.size and int(np.abs(bin_edges).max()) > lim):
+                raise NotImplementedError(
+                    "histogram: integer edges with int64 data beyond 2**53 "
+                    "are not supported (bins are compared in float64)")
+    n = _hist_counts(a, mode, edges, len(bin_edges) - 1)
+    if density:
+        # NumPy's order of operations: n / diff(edges) / n.sum()
+        db = fromarray(np.array(np.diff(bin_edges), float))
+        return db._binop(n, "div", reverse=True)._binop(
+            n.sum(), "div"), bin_edges
+    return n, bin_edges
+
+
+def bincount(x, weights=None, minlength=0):
+    """numpy.bincount for 1-D integer or bool ramba arrays; weights= is not
+    supported."""
+    if not isinstance(x, ndarray):
+        if isinstance(weights, ndarray):
+            weights = weights.asarray()
+        return np.bincount(x, weights=weights, minlength=minlength)
+    if weights is not None:
+        raise NotImplementedError(
+            "bincount: weights= is not supported (a float scatter-add with "
+            "a fixed summation order is a different kernel)")
+    if x.dtype.kind not in "biu":
+        raise TypeError(f"Cannot cast array data from {x.dtype!r} to "
+                        "dtype('int64') according to the rule 'safe'")
+    if x.ndim != 1:
+        raise ValueError("object too deep for desired array")
+    minlength = operator.index(minlength)
+    if minlength < 0:
+        raise ValueError("'minlength' must not be negative")
+    if x.size == 0:
+        return zeros(minlength, dtype=np.int64)
+    lo, hi = (int(v) for v in _hist_min_max(x))
+    if lo < 0:
+        raise ValueError("'list' argument must have no negative elements")
+    return _hist_counts(x, _hg.INDEX, None, max(hi + 1, minlength))
+
+
+def _hist_unsupported(name):
+    def f(*args, **kwargs):
+        raise NotImplementedError(
+            f"{name} is not supported on ramba arrays; histogram and "
+            "bincount are")
+    f.__name__ = name
+    return f
+
+
+histogram2d = _hist_unsupported("histogram2d")
+histogramdd = _hist_unsupported("histogramdd")
+
+ndarray._ARRAY_FUNC.update({
+    "histogram": histogram, "bincount": bincount,
+    "histogram2d": histogram2d, "histogramdd": histogramdd,
 })
 
 

@@ -1404,3 +1404,76 @@ def arg_reduce_op(self, arr, axis, kind, skipna):
 
 
 Runtime.arg_reduce_op = arg_reduce_op
+
+
+# ---------------------------------------------------------------------------
+# histogram / bincount (numpy.histogram, numpy.bincount; the reference has
+# neither).  A keyed count: every rank bins the exec box of the view that it
+# owns into a partial int64[nbins] (the hist_partial hook, ramba_amd/
+# histogram.py), then sends every owner of the result the slice of the
+# partial that the owner holds; owners add what arrives into the zeroed
+# result (rt_combine_box, op add, on HIP).  Integer adds: the counts do not
+# depend on the order of arrival.
+# ---------------------------------------------------------------------------
+
+def hist_op(self, arr, mode, edges, nbins):
+    """The int64 counts of length `nbins`, default divisions, as a bdarray."""
+    from .histogram import INDEX, hooks_for
+    bd, v = arr.bdarray, arr.view
+    hooks = hooks_for(self.backend)
+    known = getattr(hooks, "hist_dtypes", None)     # None: any NumPy dtype
+    if known is not None and str(np.dtype(bd.dtype)) not in known:
+        raise NotImplementedError(
+            f"histogram / bincount: no binning kernel for dtype {bd.dtype}")
+    out_dtype = np.dtype(np.int64)
+    out_bd = self.new_result((nbins,), out_dtype,
+                             default_divisions(self.world, (nbins,)))
+    self.backend.fill_container(out_bd, self, 0)
+
+    lbs = exec_boxes(v, bd.divisions)
+    lb = lbs[self.rank]
+    part = bad = None
+    if lb is not None:
+        part, bad = hooks.hist_partial(bd, self, v, lb, mode, edges, nbins)
+
+    cores = [self.core_box(out_bd, s) for s in range(self.world)]
+    sends, recvs, merges = [], [], []
+    for src in range(self.world):
+        if lbs[src] is None:
+            continue
+        for dst, bx in enumerate(cores):
+            if bx is None:
+                continue
+            if src == self.rank:
+                piece = part[int(bx[0, 0]):int(bx[1, 0]) + 1].contiguous()
+                if dst == self.rank:
+                    merges.append((bx, piece))
+                else:
+                    sends.append((dst, piece))
+            elif dst == self.rank:
+                buf = self.backend.new_message_buffer(box_shape(bx),
+                                                      out_dtype)
+                recvs.append((src, buf))
+                merges.append((bx, buf))
+    if sends or recvs:
+        self.backend.exchange(sends, recvs)
+    for (bx, buf) in merges:
+        self.backend.combine_box_into_container(out_bd, self, bx, buf, "sum")
+    self.backend.free_temps()
+    # the frontend validates bincount's range, so the kernel's counter of
+    # skipped elements stays zero; read after the exchange, where every
+    # rank has done its part, and summed over the ranks so that all raise
+    # or none does
+    nbad = np.int64(int(bad.cpu()[0])
+                    if mode == INDEX and bad is not None else 0)
+    if mode == INDEX and self.world > 1:
+        nbad = self.backend.allreduce(nbad, "sum")
+    if nbad:
+        raise IndexError(
+            f"bincount: {nbad} element(s) outside [0, {nbins}) reached the "
+            "binning kernel and were skipped (frontend validation was "
+            "bypassed)")
+    return out_bd
+
+
+Runtime.hist_op = hist_op
