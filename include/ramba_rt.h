@@ -24,6 +24,10 @@
  *   rt_gemm_batched   — the same for N-D (batched) operands
  *   rt_gemv           — the same for one 1-D operand (A @ x, x @ A)
  *   rt_hist           — histogram / bincount (no reference counterpart)
+ *   rt_sort           — stable radix sort of a dense run, optional payload
+ *   rt_sort_lines     — stable sort of many short lines (sort / argsort
+ *                       along an axis; no reference counterpart)
+ *   rt_sort_bounds    — lower bounds of splitter keys in a sorted run
  *   rt_stream_sync /
  *   rt_device_sync    — worker-side completion (sync, ramba.py:9843)
  *   rt_event_*        — hot-loop timing (add_time, ramba.py:945-1022)
@@ -78,7 +82,8 @@ int rt_launch(void *kernel, unsigned gx, unsigned gy, unsigned gz,
               size_t argsize);
 
 /* Argument contract shared by rt_copy_box, rt_combine_box, rt_cumsum,
- * rt_mask_compact, rt_axis_scan, rt_flat_copy and rt_hist (the contract of
+ * rt_mask_compact, rt_axis_scan, rt_flat_copy, rt_hist and the rt_sort
+ * family (the contract of
  * rt_take_rows): every argument is checked on the host before any HIP call
  * and a bad one returns nonzero with rt_last_error() naming the entry point
  * and the argument.  Rejected: nd out of range; NULL shape / strides; a
@@ -366,6 +371,75 @@ int rt_hist(uintptr_t stream, const void *in, int64_t in_off, int nd,
 int rt_hist_regime(int64_t nbins);
 int rt_hist_geometry(int *grid_cap, int *block, int64_t *wave_max_bins,
                      int64_t *block_max_bins, int64_t *edges_lds_max);
+
+/* sort / argsort — numpy.sort / numpy.argsort with kind="stable" (the
+ * reference has neither).  The order is defined ONCE, in ramba_sortkey.h:
+ * every digit and comparison reads rt_sort_canon(raw bits) (integers by
+ * value; floats -inf < .. < -0.0 == +0.0 < .. < +inf < NaN, all NaNs equal),
+ * ties go to the lower position, and the kernels move the raw bits, so zero
+ * signs and NaN payloads arrive as they were.  dtype: any rt_dtype.
+ *
+ * rt_sort, the LONG regime: a dense run of n keys at `in` sorted into `out`,
+ * a stable LSD radix sort with 8-bit digits, one pass per key byte.  With
+ * vals_out != NULL every key carries an int64 payload, read from vals_in or,
+ * when vals_in is NULL, generated as val0 + position; the sorted payloads
+ * land in vals_out (vals_in = NULL, val0 = 0 is argsort).  With vals_out ==
+ * NULL the payload is dropped and vals_in is not read.  One up-front read
+ * builds the histogram of every digit position; the host reads it back (the
+ * call synchronises the stream once) and skips each pass whose digit is the
+ * same in all n keys; *passes_run (may be NULL) is how many ran.  A live
+ * pass is three launches: per-block digit counts, one scan block per digit,
+ * scatter.  No kernel waits for another block.  Passes ping-pong between out
+ * and the scratch so that the last one writes out (and vals_out); with no
+ * live pass the run is copied.  `in` / vals_in are only read and must not
+ * overlap out, vals_out or the scratch.  At most grid_cap blocks run, each
+ * over a contiguous range of tiles of block x keys_per_lane keys.
+ * scratch: device memory, 16-byte aligned, of at least rt_sort_scratch(n,
+ * dtype, vals_out != NULL) bytes: 16 KB of histograms, 12 bytes per digit
+ * and block of counters (at most 6 MB), and one copy of the keys (and of the
+ * payloads).
+ * Validated before any HIP call: dtype, n < 0 or >= 2^40, NULL in / out /
+ * scratch with work to do, a misaligned or too small scratch.  n == 0
+ * returns 0 without launching.
+ *
+ * rt_sort_lines: nlines independent lines of len <= line_max elements of a
+ * strided box (line l, element e at in + in_off + l * line_stride + e *
+ * elem_stride, in elements, any sign), sorted into dense C-order
+ * out_keys[nlines][len] (raw keys), out_pos[nlines][len] (int64 positions
+ * 0 .. len-1, argsort), or both; either may be NULL.  Regimes: WAVE, len <=
+ * wave_max (64): one line per wave, four per block, a bitonic network in
+ * registers on the composite (canonical key, position); BLOCK, len <=
+ * line_max: one line per block, the same network in LDS.  The composite is a
+ * total order, so the network is stable; padding sorts after every element,
+ * NaN included, and is never written.  More than lines_per_launch lines take
+ * several launches.
+ * Validated before any HIP call: dtype, negative nlines / len, nlines >=
+ * 2^40, len > line_max, nlines x len > 2^46, NULL in, both outputs NULL.  A
+ * zero extent returns 0 without launching.
+ *
+ * rt_sort_bounds: for m splitter keys (device, raw bits of `dtype`) the
+ * lower bound of each in the sorted run of n keys, in the canonical order:
+ * bounds[i] (device int64) = the number of keys that sort strictly before
+ * splitters[i].  One thread per splitter, a binary search.  Validated before
+ * any HIP call: dtype, n, m < 0 or >= 2^31, NULL pointers with work to do;
+ * m == 0 returns 0.
+ *
+ * rt_sort_scratch (-1 for a bad n or dtype) and rt_sort_geometry (the
+ * compiled-in constants; line_max: 4 values, for key widths 1, 2, 4 and 8
+ * bytes; any pointer may be NULL) are host arithmetic only. */
+int rt_sort(uintptr_t stream, const void *in, void *out, const void *vals_in,
+            int64_t val0, void *vals_out, int64_t n, int dtype, void *scratch,
+            int64_t scratch_bytes, int *passes_run);
+int64_t rt_sort_scratch(int64_t n, int dtype, int with_payload);
+int rt_sort_lines(uintptr_t stream, const void *in, int64_t in_off,
+                  int64_t nlines, int64_t len, int64_t line_stride,
+                  int64_t elem_stride, int dtype, void *out_keys,
+                  void *out_pos);
+int rt_sort_bounds(uintptr_t stream, const void *run, int64_t n, int dtype,
+                   const void *splitters, int64_t m, void *bounds);
+int rt_sort_geometry(int *block, int *keys_per_lane, int *grid_cap,
+                     int *wave_max, int64_t *lines_per_launch,
+                     int64_t *line_max);
 
 int rt_stream_sync(uintptr_t stream);
 int rt_device_sync(void);

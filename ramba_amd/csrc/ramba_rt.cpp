@@ -3464,3 +3464,629 @@ extern "C" int rt_hist(uintptr_t stream, const void *in, int64_t in_off,
                                    edges_dtype, counts, bad);
     });
 }
+
+// ---------------------------------------------------------------------------
+// sort / argsort (numpy.sort, numpy.argsort; the reference has neither).
+//
+// The order is that of include/ramba_sortkey.h: every digit and comparison
+// reads rt_sort_canon(raw bits), ties go to the lower position, and the
+// kernels move the raw bits, so the result is NumPy's stable sort bit for bit.
+//
+// rt_sort, the LONG regime: a stable LSD radix sort of a dense run, 8-bit
+// digits, one pass per key byte, optionally carrying an int64 payload.
+//   sort_hist_k    one read of the keys builds the 256-bin histogram of every
+//                  digit position, in LDS per block, flushed with 64-bit
+//                  integer atomics.  The host reads the histograms back (the
+//                  call's one sync) and SKIPS every pass whose digit is the
+//                  same in all n keys.
+//   per live pass, three launches:
+//   sort_count_k   per-block digit counts, uint32, digit-major block-minor;
+//   sort_scan_k    one block per digit: the digit's base is the prefix of the
+//                  up-front histogram, the block scans its row of per-block
+//                  counts into 64-bit offsets.  No block waits for another;
+//   sort_scatter_k a block walks its contiguous range of SORT_TILE-key tiles.
+//                  A wave owns 64 x SORT_KPL consecutive keys of the tile and
+//                  takes them 64 at a time: the lanes holding a key's digit
+//                  are found with one 64-bit ballot per digit bit, the
+//                  popcount of that mask below the lane is the key's rank
+//                  among them, and a per-wave LDS counter carries the digit's
+//                  count from one 64-key step to the next.  The wave counters
+//                  are then scanned over digits and waves (tile order), keys
+//                  and payloads are reordered through LDS, and each digit's
+//                  run leaves as one contiguous global write.  Lanes past n
+//                  take part in every ballot and are masked out of every
+//                  count and store.
+// The count is NOT fused into the previous pass's scatter.  Passes ping-pong
+// between the output buffer and the scratch so that the last live pass
+// writes the output buffer whatever their number; with none live the run is
+// copied.  The grid is capped at SORT_GRID_CAP blocks, so the counter scratch
+// is at most 256 x SORT_GRID_CAP x 12 bytes.
+//
+// rt_sort_lines, short lines: the composite (canonical key, position) is a
+// total order, so a bitonic network on it is a stable sort.
+//   WAVE   len <= 64: one line per wave, four per block, one element per
+//          lane, compare-exchange by __shfl_xor over the line's power of two;
+//   BLOCK  len <= SORT_LINE_MAX: one line per block, keys and uint16
+//          positions staged once in LDS (at most 4096 x 10 B = 40 KB).
+// Padding is (all ones, position >= len): after every real element, NaN
+// included, and never written.  The raw bits are re-read at the sorted
+// positions when keys are asked for.
+// ---------------------------------------------------------------------------
+
+#include "../../include/ramba_sortkey.h"
+
+namespace {
+
+enum {
+    SORT_BLOCK = 256,
+    SORT_KPL = 8,                           // keys per lane
+    SORT_TILE = SORT_BLOCK * SORT_KPL,
+    SORT_GRID_CAP = 2048,                   // 256 CUs x 8 blocks
+    SORT_WAVE_MAX = 64,
+    SORT_LINE_MAX = 4096,                   // every key width
+    SORT_LINES_PER_LAUNCH = 1 << 22
+};
+
+template <typename T>
+using SortU = typename rt_sort_key<T>::U;
+
+struct SortPlan {
+    int64_t ntiles, tpb;    // tiles, tiles per block
+    int nblocks;
+};
+
+SortPlan sort_plan(int64_t n) {
+    SortPlan p;
+    p.ntiles = (n + SORT_TILE - 1) / SORT_TILE;
+    p.tpb = (p.ntiles + SORT_GRID_CAP - 1) / SORT_GRID_CAP;
+    if (p.tpb < 1) p.tpb = 1;
+    p.nblocks = (int)((p.ntiles + p.tpb - 1) / p.tpb);
+    return p;
+}
+
+// byte offsets of the parts of rt_sort's scratch
+struct SortScratch {
+    size_t hist, offs, counts, vals, keys, total;
+};
+
+SortScratch sort_scratch(int64_t n, int ksize, bool pay) {
+    const SortPlan p = sort_plan(n);
+    SortScratch s;
+    s.hist = 0;
+    s.offs = 8 * 256 * sizeof(uint64_t);
+    s.counts = s.offs + (size_t)256 * p.nblocks * sizeof(uint64_t);
+    s.vals = s.counts + (size_t)256 * p.nblocks * sizeof(uint32_t);
+    s.keys = s.vals + (pay ? (size_t)n * sizeof(int64_t) : 0);
+    s.total = s.keys + (((size_t)n * ksize + 15) & ~(size_t)15);
+    return s;
+}
+
+template <typename T>
+__device__ __forceinline__ unsigned sort_digit(SortU<T> raw, int shift) {
+    return (unsigned)(rt_sort_canon<T>(raw) >> shift) & 255u;
+}
+
+// One count per valid lane into cnt[d] (LDS).  When every valid lane of the
+// wave holds the same digit one lane adds the lane count (constant bytes of
+// small-range data).  Call from wave-uniform control flow.
+__device__ __forceinline__ void sort_count_add(uint32_t *cnt, unsigned d,
+                                               bool valid) {
+    const unsigned long long act = __ballot(valid);
+    if (act == 0) return;
+    const int lead = __ffsll((long long)act) - 1;
+    const unsigned d0 = (unsigned)__shfl((int)d, lead);
+    if (__ballot(valid && d != d0) == 0) {
+        if ((int)(threadIdx.x & 63) == lead)
+            atomicAdd(&cnt[d0], (uint32_t)__popcll(act));
+    } else if (valid) {
+        atomicAdd(&cnt[d], 1u);
+    }
+}
+
+__global__ __launch_bounds__(256) void sort_zero_k(unsigned long long *p,
+                                                   int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) p[i] = 0;
+}
+
+// histograms of every digit position; block b reads keys [b, b+1) x per_block
+template <typename T>
+__global__ __launch_bounds__(256) void sort_hist_k(
+    const SortU<T> *__restrict__ keys, int64_t n, int64_t per_block,
+    unsigned long long *__restrict__ hist) {
+    constexpr int NB = (int)sizeof(T);
+    __shared__ uint32_t cnt[NB][256];
+    const int t = threadIdx.x;
+#pragma unroll
+    for (int b = 0; b < NB; ++b) cnt[b][t] = 0;
+    __syncthreads();
+    const int64_t lo = (int64_t)blockIdx.x * per_block;
+    const int64_t hi = lo + per_block < n ? lo + per_block : n;
+    for (int64_t i0 = lo; i0 < hi; i0 += 256) {
+        const int64_t i = i0 + t;
+        const bool valid = i < hi;
+        const SortU<T> c = valid ? rt_sort_canon<T>(keys[i]) : (SortU<T>)0;
+#pragma unroll
+        for (int b = 0; b < NB; ++b)
+            sort_count_add(cnt[b], (unsigned)(c >> (8 * b)) & 255u, valid);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        const uint32_t v = cnt[b][t];
+        if (v) atomicAdd(&hist[b * 256 + t], (unsigned long long)v);
+    }
+}
+
+// counts[d * nblocks + b]: keys of block b's tile range with digit d
+template <typename T>
+__global__ __launch_bounds__(256) void sort_count_k(
+    const SortU<T> *__restrict__ keys, int64_t n, int64_t per_block,
+    int shift, uint32_t *__restrict__ counts) {
+    __shared__ uint32_t cnt[256];
+    const int t = threadIdx.x;
+    cnt[t] = 0;
+    __syncthreads();
+    const int64_t lo = (int64_t)blockIdx.x * per_block;
+    const int64_t hi = lo + per_block < n ? lo + per_block : n;
+    for (int64_t i0 = lo; i0 < hi; i0 += 256) {
+        const int64_t i = i0 + t;
+        const bool valid = i < hi;
+        const unsigned d = valid ? sort_digit<T>(keys[i], shift) : 0u;
+        sort_count_add(cnt, d, valid);
+    }
+    __syncthreads();
+    counts[(int64_t)t * gridDim.x + blockIdx.x] = cnt[t];
+}
+
+__device__ __forceinline__ unsigned long long sort_wave_incl(
+    unsigned long long x, int lane) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned long long y = __shfl_up(x, off);
+        if (lane >= off) x += y;
+    }
+    return x;
+}
+
+// block d: offs[d][b] = (keys with a lower digit) + (keys of digit d in the
+// blocks before b).  totals: the 256 bins of this digit position.
+__global__ __launch_bounds__(256) void sort_scan_k(
+    const uint32_t *__restrict__ counts,
+    const unsigned long long *__restrict__ totals,
+    unsigned long long *__restrict__ offs, int nblocks) {
+    __shared__ unsigned long long red[4], wsum[4];
+    const int t = threadIdx.x, w = t >> 6, lane = t & 63;
+    const int d = blockIdx.x;
+    const unsigned long long h =
+        sort_wave_incl(t < d ? totals[t] : 0ull, lane);
+    const int per = (nblocks + 255) / 256;
+    const int lo = t * per < nblocks ? t * per : nblocks;
+    const int hi = lo + per < nblocks ? lo + per : nblocks;
+    const uint32_t *row = counts + (int64_t)d * nblocks;
+    unsigned long long s = 0;
+    for (int i = lo; i < hi; ++i) s += row[i];
+    const unsigned long long x = sort_wave_incl(s, lane);
+    if (lane == 63) {
+        red[w] = h;
+        wsum[w] = x;
+    }
+    __syncthreads();
+    unsigned long long run = red[0] + red[1] + red[2] + red[3] + x - s;
+    for (int k = 0; k < w; ++k) run += wsum[k];
+    unsigned long long *orow = offs + (int64_t)d * nblocks;
+    for (int i = lo; i < hi; ++i) {
+        orow[i] = run;
+        run += row[i];
+    }
+}
+
+template <typename T, bool PAY>
+__global__ __launch_bounds__(256) void sort_scatter_k(
+    const SortU<T> *__restrict__ kin, SortU<T> *__restrict__ kout,
+    const int64_t *__restrict__ vin, int64_t *__restrict__ vout, int64_t val0,
+    const unsigned long long *__restrict__ offs, int64_t n, int shift,
+    int64_t tpb, int64_t ntiles) {
+    using U = SortU<T>;
+    constexpr int EXB = PAY ? 8 : (int)sizeof(U);
+    __shared__ __attribute__((aligned(16))) unsigned char exraw[SORT_TILE * EXB];
+    __shared__ uint32_t cnt[4][256];    // per wave, per digit
+    __shared__ uint32_t tstart[256];    // first slot of a digit in the tile
+    __shared__ uint32_t wsum[4];
+    __shared__ int64_t gbase[256];      // next global slot of a digit
+    U *exk = reinterpret_cast<U *>(exraw);
+    int64_t *exv = reinterpret_cast<int64_t *>(exraw);
+    const int t = threadIdx.x, w = t >> 6, lane = t & 63;
+    const unsigned long long lt_mask = (1ull << lane) - 1ull;
+    volatile uint32_t *wc = cnt[w];
+
+    gbase[t] = (int64_t)offs[(int64_t)t * gridDim.x + blockIdx.x];
+    const int64_t tile0 = (int64_t)blockIdx.x * tpb;
+    const int64_t tile1 = tile0 + tpb < ntiles ? tile0 + tpb : ntiles;
+    for (int64_t tile = tile0; tile < tile1; ++tile) {
+        const int64_t base = tile * SORT_TILE;
+        const int64_t first = base + w * (64 * SORT_KPL) + lane;
+        cnt[0][t] = cnt[1][t] = cnt[2][t] = cnt[3][t] = 0;
+        __syncthreads();
+
+        U key[SORT_KPL];
+        int64_t pv[PAY ? SORT_KPL : 1];
+        uint32_t rank[SORT_KPL];
+#pragma unroll
+        for (int j = 0; j < SORT_KPL; ++j) {
+            const int64_t i = first + j * 64;
+            const bool valid = i < n;
+            key[j] = valid ? kin[i] : (U)0;
+            if (PAY) pv[j] = !valid ? 0 : vin ? vin[i] : val0 + i;
+        }
+#pragma unroll
+        for (int j = 0; j < SORT_KPL; ++j) {
+            const bool valid = first + j * 64 < n;
+            const unsigned d = sort_digit<T>(key[j], shift);
+            // lanes of this wave that are valid and hold digit d
+            unsigned long long mask = __ballot(valid);
+#pragma unroll
+            for (int b = 0; b < 8; ++b) {
+                const bool bit = (d >> b) & 1u;
+                const unsigned long long bal = __ballot(bit);
+                mask &= bit ? bal : ~bal;
+            }
+            const uint32_t below = (uint32_t)__popcll(mask & lt_mask);
+            const uint32_t prev = wc[d];
+            __builtin_amdgcn_wave_barrier();
+            if (valid && below == 0) wc[d] = prev + (uint32_t)__popcll(mask);
+            __builtin_amdgcn_wave_barrier();
+            rank[j] = prev + below;
+        }
+        __syncthreads();
+
+        // digits scanned over the tile, waves in tile order within a digit
+        const uint32_t c0 = cnt[0][t], c1 = cnt[1][t], c2 = cnt[2][t],
+                       c3 = cnt[3][t];
+        const uint32_t tot = c0 + c1 + c2 + c3;
+        uint32_t x = tot;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t y = __shfl_up(x, off);
+            if (lane >= off) x += y;
+        }
+        if (lane == 63) wsum[w] = x;
+        __syncthreads();
+        uint32_t excl = x - tot;
+        for (int k = 0; k < w; ++k) excl += wsum[k];
+        cnt[0][t] = excl;
+        cnt[1][t] = excl + c0;
+        cnt[2][t] = excl + c0 + c1;
+        cnt[3][t] = excl + c0 + c1 + c2;
+        tstart[t] = excl;
+        __syncthreads();
+
+#pragma unroll
+        for (int j = 0; j < SORT_KPL; ++j) {
+            if (first + j * 64 < n) {
+                rank[j] += cnt[w][sort_digit<T>(key[j], shift)];
+                exk[rank[j]] = key[j];
+            }
+        }
+        __syncthreads();
+        const int64_t left = n - base;
+        const int nvalid = left < SORT_TILE ? (int)left : (int)SORT_TILE;
+        int64_t dst[SORT_KPL];
+#pragma unroll
+        for (int j = 0; j < SORT_KPL; ++j) {
+            const int q = j * 256 + t;
+            if (q < nvalid) {
+                const U k = exk[q];
+                const unsigned d = sort_digit<T>(k, shift);
+                dst[j] = gbase[d] + (int64_t)(q - (int)tstart[d]);
+                kout[dst[j]] = k;
+            }
+        }
+        if (PAY) {
+            __syncthreads();
+#pragma unroll
+            for (int j = 0; j < SORT_KPL; ++j)
+                if (first + j * 64 < n) exv[rank[j]] = pv[j];
+            __syncthreads();
+#pragma unroll
+            for (int j = 0; j < SORT_KPL; ++j)
+                if (j * 256 + t < nvalid) vout[dst[j]] = exv[j * 256 + t];
+        }
+        __syncthreads();
+        gbase[t] += tot;
+    }
+}
+
+// every pass skipped: the run is already in order
+template <typename U>
+__global__ __launch_bounds__(256) void sort_copy_k(
+    const U *__restrict__ kin, U *__restrict__ kout,
+    const int64_t *__restrict__ vin, int64_t *__restrict__ vout, int64_t val0,
+    int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * 256) {
+        kout[i] = kin[i];
+        if (vout) vout[i] = vin ? vin[i] : val0 + i;
+    }
+}
+
+template <typename T>
+int sort_run(uintptr_t stream, const void *in, void *out, const void *vals_in,
+             int64_t val0, void *vals_out, int64_t n, void *scratch,
+             int *passes_run) {
+    using U = SortU<T>;
+    constexpr int NB = (int)sizeof(T);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const bool pay = vals_out != nullptr;
+    const SortPlan p = sort_plan(n);
+    const SortScratch s = sort_scratch(n, NB, pay);
+    char *sc = static_cast<char *>(scratch);
+    auto *hist = reinterpret_cast<unsigned long long *>(sc + s.hist);
+    auto *offs = reinterpret_cast<unsigned long long *>(sc + s.offs);
+    auto *counts = reinterpret_cast<uint32_t *>(sc + s.counts);
+    const int64_t per_block = p.tpb * SORT_TILE;
+
+    sort_zero_k<<<NB, 256, 0, st>>>(hist, NB * 256);
+    sort_hist_k<T><<<p.nblocks, 256, 0, st>>>(static_cast<const U *>(in), n,
+                                              per_block, hist);
+    if (launched("rt_sort histogram")) return 1;
+    unsigned long long host[NB * 256];
+    HIP_CHECK(hipMemcpyAsync(host, hist, sizeof(host), hipMemcpyDeviceToHost,
+                             st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    int live[NB], nlive = 0;
+    for (int b = 0; b < NB; ++b) {
+        bool one = false;
+        for (int d = 0; d < 256; ++d)
+            if (host[b * 256 + d] == (unsigned long long)n) one = true;
+        if (!one) live[nlive++] = b;
+    }
+    if (passes_run) *passes_run = nlive;
+
+    const U *kin = static_cast<const U *>(in);
+    const int64_t *vin = static_cast<const int64_t *>(vals_in);
+    if (nlive == 0) {
+        const int64_t want = (n + 255) / 256;
+        sort_copy_k<U><<<(unsigned)(want < 4096 ? want : 4096), 256, 0, st>>>(
+            kin, static_cast<U *>(out), vin,
+            static_cast<int64_t *>(vals_out), val0, n);
+        return launched("rt_sort copy");
+    }
+    for (int k = 0; k < nlive; ++k) {
+        const bool to_out = ((nlive - k) & 1) != 0;
+        U *kout = to_out ? static_cast<U *>(out)
+                         : reinterpret_cast<U *>(sc + s.keys);
+        int64_t *vout = !pay     ? nullptr
+                        : to_out ? static_cast<int64_t *>(vals_out)
+                                 : reinterpret_cast<int64_t *>(sc + s.vals);
+        const int shift = 8 * live[k];
+        sort_count_k<T><<<p.nblocks, 256, 0, st>>>(kin, n, per_block, shift,
+                                                   counts);
+        sort_scan_k<<<256, 256, 0, st>>>(counts, hist + live[k] * 256, offs,
+                                         p.nblocks);
+        if (pay)
+            sort_scatter_k<T, true><<<p.nblocks, 256, 0, st>>>(
+                kin, kout, vin, vout, val0, offs, n, shift, p.tpb, p.ntiles);
+        else
+            sort_scatter_k<T, false><<<p.nblocks, 256, 0, st>>>(
+                kin, kout, nullptr, nullptr, 0, offs, n, shift, p.tpb,
+                p.ntiles);
+        if (launched("rt_sort pass")) return 1;
+        kin = kout;
+        vin = vout;
+    }
+    return 0;
+}
+
+template <typename U>
+__device__ __forceinline__ U sort_shfl_xor(U v, int j) {
+    if constexpr (sizeof(U) == 8)
+        return (U)__shfl_xor((unsigned long long)v, j);
+    else
+        return (U)__shfl_xor((unsigned)v, j);
+}
+
+// WAVE: one line per wave.  S: the power of two >= len.
+template <typename T>
+__global__ __launch_bounds__(256) void sort_lines_wave_k(
+    const SortU<T> *__restrict__ in, int64_t nlines, int len, int S,
+    int64_t ls, int64_t es, SortU<T> *__restrict__ out_keys,
+    int64_t *__restrict__ out_pos) {
+    using U = SortU<T>;
+    const int lane = threadIdx.x & 63;
+    const int64_t line = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (line >= nlines) return;             // a whole wave leaves together
+    const U *src = in + line * ls;
+    U ck = lane < len ? rt_sort_canon<T>(src[lane * es]) : (U) ~(U)0;
+    int pos = lane;
+    for (int k = 2; k <= S; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            const U ok = sort_shfl_xor<U>(ck, j);
+            const int op = __shfl_xor(pos, j);
+            const bool want_min = ((lane & k) == 0) == ((lane & j) == 0);
+            const bool other_less = ok < ck || (ok == ck && op < pos);
+            if (other_less == want_min) {
+                ck = ok;
+                pos = op;
+            }
+        }
+    }
+    if (lane < len) {
+        if (out_keys) out_keys[line * len + lane] = src[pos * es];
+        if (out_pos) out_pos[line * len + lane] = pos;
+    }
+}
+
+// BLOCK: one line per block, P = the power of two >= len slots in LDS.
+template <typename T>
+__global__ __launch_bounds__(256) void sort_lines_block_k(
+    const SortU<T> *__restrict__ in, int len, int P, int64_t ls, int64_t es,
+    SortU<T> *__restrict__ out_keys, int64_t *__restrict__ out_pos) {
+    using U = SortU<T>;
+    extern __shared__ __attribute__((aligned(16))) unsigned char sort_lds[];
+    U *ck = reinterpret_cast<U *>(sort_lds);
+    uint16_t *ps = reinterpret_cast<uint16_t *>(sort_lds + (size_t)P * sizeof(U));
+    const int t = threadIdx.x;
+    const int64_t line = blockIdx.x;
+    const U *src = in + line * ls;
+    for (int q = t; q < P; q += 256) {
+        ck[q] = q < len ? rt_sort_canon<T>(src[q * es]) : (U) ~(U)0;
+        ps[q] = (uint16_t)q;
+    }
+    __syncthreads();
+    for (int k = 2; k <= P; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int idx = t; idx < (P >> 1); idx += 256) {
+                const int lo = ((idx & ~(j - 1)) << 1) | (idx & (j - 1));
+                const int hi = lo | j;
+                const U a = ck[lo], b = ck[hi];
+                const uint16_t pa = ps[lo], pb = ps[hi];
+                const bool b_less = b < a || (b == a && pb < pa);
+                if (b_less == ((lo & k) == 0)) {
+                    ck[lo] = b;
+                    ck[hi] = a;
+                    ps[lo] = pb;
+                    ps[hi] = pa;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    for (int q = t; q < len; q += 256) {
+        const int pos = ps[q];
+        if (out_keys) out_keys[line * len + q] = src[pos * es];
+        if (out_pos) out_pos[line * len + q] = pos;
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void sort_bounds_k(
+    const SortU<T> *__restrict__ run, int64_t n,
+    const SortU<T> *__restrict__ spl, int64_t m, int64_t *__restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= m) return;
+    const SortU<T> s = rt_sort_canon<T>(spl[i]);
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (rt_sort_canon<T>(run[mid]) < s)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    out[i] = lo;
+}
+
+int sort_pow2(int64_t len) {
+    int p = 1;
+    while (p < len) p <<= 1;
+    return p;
+}
+
+}  // namespace
+
+extern "C" int rt_sort_geometry(int *block, int *keys_per_lane, int *grid_cap,
+                                int *wave_max, int64_t *lines_per_launch,
+                                int64_t *line_max) {
+    if (block) *block = SORT_BLOCK;
+    if (keys_per_lane) *keys_per_lane = SORT_KPL;
+    if (grid_cap) *grid_cap = SORT_GRID_CAP;
+    if (wave_max) *wave_max = SORT_WAVE_MAX;
+    if (lines_per_launch) *lines_per_launch = SORT_LINES_PER_LAUNCH;
+    if (line_max)
+        for (int k = 0; k < 4; ++k) line_max[k] = SORT_LINE_MAX;
+    return 0;
+}
+
+extern "C" int64_t rt_sort_scratch(int64_t n, int dtype, int with_payload) {
+    if (n < 0 || n >= (1LL << 40) || dtype < RT_F64 || dtype > RT_U8)
+        return -1;
+    return (int64_t)sort_scratch(n, dtype_size(dtype), with_payload != 0)
+        .total;
+}
+
+extern "C" int rt_sort(uintptr_t stream, const void *in, void *out,
+                       const void *vals_in, int64_t val0, void *vals_out,
+                       int64_t n, int dtype, void *scratch,
+                       int64_t scratch_bytes, int *passes_run) {
+    const char *who = "rt_sort";
+    if (dtype < RT_F64 || dtype > RT_U8) return fail(who, "bad dtype");
+    if (n < 0) return fail(who, "negative n");
+    if (n >= (1LL << 40)) return fail(who, "n out of range");
+    if (passes_run) *passes_run = 0;
+    if (n == 0) return 0;
+    if (!in) return fail(who, "NULL in");
+    if (!out) return fail(who, "NULL out");
+    if (!scratch) return fail(who, "NULL scratch");
+    if (reinterpret_cast<uintptr_t>(scratch) & 15)
+        return fail(who, "scratch not 16-byte aligned");
+    if (scratch_bytes < rt_sort_scratch(n, dtype, vals_out != nullptr))
+        return fail(who, "scratch_bytes too small (rt_sort_scratch)");
+    return dtype_dispatch<7>(who, dtype, [&](auto t) {
+        return sort_run<decltype(t)>(stream, in, out, vals_in, val0, vals_out,
+                                     n, scratch, passes_run);
+    });
+}
+
+extern "C" int rt_sort_lines(uintptr_t stream, const void *in, int64_t in_off,
+                             int64_t nlines, int64_t len, int64_t line_stride,
+                             int64_t elem_stride, int dtype, void *out_keys,
+                             void *out_pos) {
+    const char *who = "rt_sort_lines";
+    if (dtype < RT_F64 || dtype > RT_U8) return fail(who, "bad dtype");
+    if (nlines < 0) return fail(who, "negative nlines");
+    if (len < 0) return fail(who, "negative len");
+    if (nlines >= (1LL << 40)) return fail(who, "nlines out of range");
+    if (len > SORT_LINE_MAX) return fail(who, "len exceeds line_max");
+    if (nlines == 0 || len == 0) return 0;
+    if (nlines > (1LL << 46) / len)
+        return fail(who, "nlines x len too large");
+    if (!in) return fail(who, "NULL in");
+    if (!out_keys && !out_pos) return fail(who, "NULL out_keys and out_pos");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    return dtype_dispatch<7>(who, dtype, [&](auto t) {
+        using T = decltype(t);
+        using U = SortU<T>;
+        const int P = sort_pow2(len);
+        for (int64_t l0 = 0; l0 < nlines; l0 += SORT_LINES_PER_LAUNCH) {
+            const int64_t nl = nlines - l0 < SORT_LINES_PER_LAUNCH
+                                   ? nlines - l0
+                                   : (int64_t)SORT_LINES_PER_LAUNCH;
+            const U *src = static_cast<const U *>(in) + in_off
+                           + l0 * line_stride;
+            U *ok = out_keys ? static_cast<U *>(out_keys) + l0 * len : nullptr;
+            int64_t *op =
+                out_pos ? static_cast<int64_t *>(out_pos) + l0 * len : nullptr;
+            if (len <= SORT_WAVE_MAX)
+                sort_lines_wave_k<T><<<(unsigned)((nl + 3) / 4), 256, 0, st>>>(
+                    src, nl, (int)len, P, line_stride, elem_stride, ok, op);
+            else
+                sort_lines_block_k<T>
+                    <<<(unsigned)nl, 256, (size_t)P * (sizeof(U) + 2), st>>>(
+                        src, (int)len, P, line_stride, elem_stride, ok, op);
+        }
+        return launched(who);
+    });
+}
+
+extern "C" int rt_sort_bounds(uintptr_t stream, const void *run, int64_t n,
+                              int dtype, const void *splitters, int64_t m,
+                              void *bounds) {
+    const char *who = "rt_sort_bounds";
+    if (dtype < RT_F64 || dtype > RT_U8) return fail(who, "bad dtype");
+    if (n < 0 || n >= (1LL << 40)) return fail(who, "n out of range");
+    if (m < 0 || m >= (1LL << 31)) return fail(who, "m out of range");
+    if (m == 0) return 0;
+    if (n > 0 && !run) return fail(who, "NULL run");
+    if (!splitters) return fail(who, "NULL splitters");
+    if (!bounds) return fail(who, "NULL bounds");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    return dtype_dispatch<7>(who, dtype, [&](auto t) {
+        using T = decltype(t);
+        sort_bounds_k<T><<<(unsigned)((m + 255) / 256), 256, 0, st>>>(
+            static_cast<const SortU<T> *>(run), n,
+            static_cast<const SortU<T> *>(splitters), m,
+            static_cast<int64_t *>(bounds));
+        return launched(who);
+    });
+}

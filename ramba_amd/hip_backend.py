@@ -97,6 +97,15 @@ _RT_ABI = {
     "rt_hist_regime": (_int, [_i64]),
     "rt_hist_geometry": (_int, [ctypes.POINTER(_int), ctypes.POINTER(_int),
                                 _p64, _p64, _p64]),
+    "rt_sort": (_int, [_sz, _vp, _vp, _vp, _i64, _vp, _i64, _int, _vp, _i64,
+                       ctypes.POINTER(_int)]),
+    "rt_sort_scratch": (_i64, [_i64, _int, _int]),
+    "rt_sort_lines": (_int, [_sz, _vp, _i64, _i64, _i64, _i64, _i64, _int,
+                             _vp, _vp]),
+    "rt_sort_bounds": (_int, [_sz, _vp, _i64, _int, _vp, _i64, _vp]),
+    "rt_sort_geometry": (_int, [ctypes.POINTER(_int), ctypes.POINTER(_int),
+                                ctypes.POINTER(_int), ctypes.POINTER(_int),
+                                _p64, _p64]),
     "rt_stream_sync": (_int, [_sz]),
     "rt_device_sync": (_int, []),
     "rt_event_create": (_int, [_pvp]),
@@ -138,6 +147,21 @@ def hist_geometry(lib):
     return {"grid_cap": cap.value, "block": blk.value,
             "wave_max_bins": wmax.value, "block_max_bins": bmax.value,
             "edges_lds_max": emax.value}
+
+
+def sort_geometry(lib):
+    """rt_sort_geometry as a dict (host arithmetic; needs no GPU).  `tile`
+    is block x keys_per_lane; `line_max` is by key width in bytes."""
+    blk, kpl, cap, wmax = (ctypes.c_int(), ctypes.c_int(), ctypes.c_int(),
+                           ctypes.c_int())
+    lpl, lmax = ctypes.c_int64(), (ctypes.c_int64 * 4)()
+    lib.rt_sort_geometry(ctypes.byref(blk), ctypes.byref(kpl),
+                         ctypes.byref(cap), ctypes.byref(wmax),
+                         ctypes.byref(lpl), lmax)
+    return {"block": blk.value, "keys_per_lane": kpl.value,
+            "tile": blk.value * kpl.value, "grid_cap": cap.value,
+            "wave_max": wmax.value, "lines_per_launch": lpl.value,
+            "line_max": {1 << k: int(lmax[k]) for k in range(4)}}
 
 
 def _hb_arg_chunks(nd, axis, nout, K):
@@ -1187,6 +1211,119 @@ class HipBackend:
             edt, int(nbins), ctypes.c_void_p(counts.data_ptr()),
             ctypes.c_void_p(bad.data_ptr())), "rt_hist")
         return counts, bad
+
+    # -- sort / argsort (runtime.sort_op) -------------------------------------
+    #
+    # The hooks of ramba_amd/sorting.py on the rt_sort kernels.  Lines are
+    # read in place in the container; runs and results are dense tensors.
+
+    sort_dtypes = frozenset(RT_DTYPE)   # sort_op refuses any other, by name
+
+    def sort_geometry(self):
+        """The compiled-in constants of the rt_sort family, by name."""
+        if getattr(self, "_sort_geo", None) is None:
+            self._sort_geo = sort_geometry(self.lib)
+        return self._sort_geo
+
+    def _sort_long(self, keys, out_keys, vals, val0, out_vals):
+        """rt_sort of the dense 1-D `keys` into out_keys (and out_vals)."""
+        n = int(keys.numel())
+        dtc = RT_DTYPE[str(keys.dtype).replace("torch.", "")]
+        nbytes = int(self.lib.rt_sort_scratch(n, dtc, out_vals is not None))
+        scratch = self.torch.empty(nbytes, dtype=self.torch.uint8,
+                                   device="cuda")
+        passes = ctypes.c_int()
+        self._check(self.lib.rt_sort(
+            self._stream(), ctypes.c_void_p(keys.data_ptr()),
+            ctypes.c_void_p(out_keys.data_ptr()),
+            ctypes.c_void_p(vals.data_ptr()) if vals is not None else None,
+            int(val0),
+            ctypes.c_void_p(out_vals.data_ptr())
+            if out_vals is not None else None,
+            n, dtc, ctypes.c_void_p(scratch.data_ptr()), nbytes,
+            ctypes.byref(passes)), "rt_sort")
+        return passes.value
+
+    def _sort_lines(self, src, off, nlines, length, ls, es, out_keys,
+                    out_pos):
+        dtc = RT_DTYPE[str(src.dtype).replace("torch.", "")]
+        self._check(self.lib.rt_sort_lines(
+            self._stream(), ctypes.c_void_p(src.data_ptr()), int(off),
+            int(nlines), int(length), int(ls), int(es), dtc,
+            ctypes.c_void_p(out_keys.data_ptr())
+            if out_keys is not None else None,
+            ctypes.c_void_p(out_pos.data_ptr())
+            if out_pos is not None else None), "rt_sort_lines")
+
+    def sort_lines(self, bd, rt, out_bd, want_index):
+        d, _, cstr, pads = rt.shard_geometry(bd)
+        if d is None:
+            return
+        nl, length = (int(x) for x in box_shape(d))
+        cont = self._cont(bd)
+        off = pads[0] * cstr[0] + pads[1] * cstr[1]
+        res = self.torch.empty(
+            (nl, length), device="cuda",
+            dtype=self.torch.int64 if want_index else cont.dtype)
+        if length <= self.sort_geometry()["line_max"][cont.element_size()]:
+            self._sort_lines(cont, off, nl, length, cstr[0], cstr[1],
+                             None if want_index else res,
+                             res if want_index else None)
+        else:
+            # long lines are few: one radix sort per line.  A row of the
+            # container is a dense run (cstr[1] == 1).
+            core = cont[pads[0]:pads[0] + nl, pads[1]:pads[1] + length]
+            keys = self.torch.empty(length, dtype=cont.dtype, device="cuda") \
+                if want_index else None
+            for i in range(nl):
+                self._sort_long(core[i], keys if want_index else res[i],
+                                None, 0, res[i] if want_index else None)
+        _, _, _, opads = rt.shard_geometry(out_bd)
+        self._cont(out_bd)[opads[0]:opads[0] + nl,
+                           opads[1]:opads[1] + length] = res
+
+    def local_run(self, bd, rt):
+        d, _, _, pads = rt.shard_geometry(bd)
+        if d is None:
+            return self.torch.empty(0, dtype=self._tdt(bd.dtype),
+                                    device="cuda")
+        n = int(d[1, 0] - d[0, 0] + 1)
+        return self._cont(bd)[pads[0]:pads[0] + n]
+
+    def sort_run(self, keys, vals, val0, want_keys, want_vals):
+        n = int(keys.numel())
+        out_k = self.torch.empty_like(keys)
+        out_v = self.torch.empty(n, dtype=self.torch.int64, device="cuda") \
+            if want_vals else None
+        if n == 0:
+            return (out_k if want_keys else None), out_v
+        if n <= self.sort_geometry()["line_max"][keys.element_size()] \
+                and vals is None:
+            self._sort_lines(keys, 0, 1, n, n, 1,
+                             out_k if want_keys else None, out_v)
+            if want_vals and val0:
+                out_v += int(val0)
+        else:
+            self._sort_long(keys.contiguous(), out_k,
+                            vals.contiguous() if vals is not None else None,
+                            val0, out_v)
+        return (out_k if want_keys else None), out_v
+
+    def sort_bounds(self, run, splitters):
+        m = int(splitters.size)
+        if m == 0:
+            return np.empty(0, dtype=np.int64)
+        spl = self.torch.from_numpy(np.ascontiguousarray(
+            splitters.view(np.uint8) if splitters.dtype == np.bool_
+            else splitters)).to("cuda")
+        out = self.torch.empty(m, dtype=self.torch.int64, device="cuda")
+        self._check(self.lib.rt_sort_bounds(
+            self._stream(),
+            ctypes.c_void_p(run.data_ptr()) if run.numel() else None,
+            int(run.numel()), RT_DTYPE[str(run.dtype).replace("torch.", "")],
+            ctypes.c_void_p(spl.data_ptr()), m,
+            ctypes.c_void_p(out.data_ptr())), "rt_sort_bounds")
+        return out.cpu().numpy()
 
     # -- cross-stage fusion (staged/tiled kernel; ramba_amd/staged.py) --------
 

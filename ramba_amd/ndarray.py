@@ -1496,6 +1496,85 @@ ndarray._ARRAY_FUNC.update({
 })
 
 
+# -- sort / argsort on runtime.sort_op.  The axis is moved last as a view,
+#    the lines are folded to (nlines, len) and brought onto contiguous axis-0
+#    divisions through the engine (what reshape and take do), each rank sorts
+#    its lines, and the result is presented through the inverse view.  A 1-D
+#    array over several ranks takes the sample sort.  Always the stable
+#    result, which satisfies every `kind`.  Sync points, like take. ---------
+
+def _sorted(a, axis, kind, order, want_index, name):
+    if not isinstance(a, ndarray):      # host data (0-d included): NumPy's
+        return getattr(np, name)(a, axis=axis, kind=kind, order=order)
+    if order is not None:
+        raise NotImplementedError(
+            f"{name}: order= (structured dtypes) is not supported")
+    if a.dtype.kind == "c":
+        raise NotImplementedError(f"{name}: complex input is not supported")
+    if a.ndim > 4:
+        raise NotImplementedError(
+            f"{name} supports arrays of up to 4 dimensions")
+    if axis is None:
+        if a.ndim != 1:
+            a = a.ravel()
+        axis = 0
+    axis = operator.index(axis)
+    nd = a.ndim
+    if not (-nd <= axis < nd):
+        raise np.exceptions.AxisError(axis, nd)
+    axis = axis + nd if axis < 0 else axis
+    if a.size == 0:
+        return zeros(a.shape, dtype=np.int64 if want_index else a.dtype)
+    rt = deferred.get_runtime()
+    if nd == 1 and rt.world > 1:
+        src = _gemm_operand(a, a.dtype, rt)
+        deferred.flush()
+        out_bd = rt.sort_op(src, 0, want_index)
+        return ndarray(out_bd, View.identity(out_bd.shape))
+    m = a.moveaxis(axis, -1) if axis != nd - 1 else a
+    length = m.shape[-1]
+    src = m if nd == 2 else m.reshape((m.size // length, length))
+    src = _gemm_operand(src, src.dtype, rt)
+    deferred.flush()
+    out_bd = rt.sort_op(src, 1, want_index)
+    res = ndarray(out_bd, View.identity(out_bd.shape))
+    if nd != 2:
+        res = res.reshape(m.shape)
+    return res.moveaxis(-1, axis) if axis != nd - 1 else res
+
+
+def sort(a, axis=-1, kind=None, order=None):
+    """numpy.sort for ramba arrays: a sorted copy, always the stable result
+    (NaN last, as NumPy), whatever `kind`.  order= and complex input are not
+    supported."""
+    return _sorted(a, axis, kind, order, False, "sort")
+
+
+def argsort(a, axis=-1, kind=None, order=None):
+    """numpy.argsort for ramba arrays: the int64 indices of the stable sort
+    along `axis` (of the flattened array for axis=None)."""
+    return _sorted(a, axis, kind, order, True, "argsort")
+
+
+def _nd_sort(self, axis=-1, kind=None, order=None):
+    """In place: the sorted result is assigned back."""
+    if axis is None:
+        raise TypeError("'NoneType' object cannot be interpreted as an "
+                        "integer")
+    self[()] = sort(self, axis=axis, kind=kind, order=order)
+
+
+ndarray.sort = _nd_sort
+ndarray.argsort = lambda self, axis=-1, kind=None, order=None: argsort(
+    self, axis=axis, kind=kind, order=order)
+ndarray._ARRAY_FUNC.update({
+    "sort": lambda a, axis=-1, kind=None, order=None, **kw:
+        sort(a, axis=axis, kind=kind, order=order),
+    "argsort": lambda a, axis=-1, kind=None, order=None, **kw:
+        argsort(a, axis=axis, kind=kind, order=order),
+})
+
+
 # remaining mod_to_array names (reference ramba.py:9697): delegate to the
 # method when given a ramba array, to numpy otherwise.  These are exported
 # through the PACKAGE namespace (ramba_amd/__init__.py), NOT injected into

@@ -1477,3 +1477,111 @@ def hist_op(self, arr, mode, edges, nbins):
 
 
 Runtime.hist_op = hist_op
+
+
+# ---------------------------------------------------------------------------
+# sort / argsort (numpy.sort, numpy.argsort, always the stable result; the
+# reference has neither).  The frontend hands over a constructed array on
+# contiguous (axis-0) divisions, sorted along its LAST axis through the hooks
+# of ramba_amd/sorting.py:
+#   2-D (nlines, len): no line is split over ranks, so every rank sorts the
+#     lines of its core and nothing is exchanged;
+#   1-D over several ranks: a sample sort with regular sampling.  Every rank
+#     sorts its box (for argsort with the global index as the payload) and
+#     contributes W-1 regularly spaced samples; the allgathered samples are
+#     sorted on the host with NumPy (the same order) and W-1 splitters taken
+#     from them.  Bucket j gets the keys k with s[j-1] <= k < s[j] in the
+#     canonical order, so all keys equal to a splitter reach one rank.  The
+#     W x W count matrix is allgathered, the segments travel with
+#     backend.exchange, and every rank sorts, stably, what it received
+#     concatenated in source-rank order.  Source-rank order is global-index
+#     order and every segment is already stable, so that second sort gives
+#     the globally stable result with no merge kernel.  The result's
+#     divisions follow the bucket sizes, as those of a[mask] do; heavy
+#     duplication can leave ranks empty or give one rank everything.
+# ---------------------------------------------------------------------------
+
+def sort_op(self, arr, axis, want_index):
+    """`arr` sorted (or argsorted: int64 positions) along `axis`, its last,
+    as a bdarray."""
+    from .sorting import hooks_for
+    bd, v = arr.bdarray, arr.view
+    nd = len(bd.shape)
+    assert axis == nd - 1 and nd in (1, 2), "sort_op: last axis of 1-D / 2-D"
+    assert bd.constructed and v.is_identity_for(bd.shape) and np.array_equal(
+        bd.divisions, contiguous_divisions(self.world, bd.shape)), \
+        "sort_op: the frontend repartitions first"
+    hooks = hooks_for(self.backend)
+    known = getattr(hooks, "sort_dtypes", None)     # None: any NumPy dtype
+    if known is not None and str(np.dtype(bd.dtype)) not in known:
+        raise NotImplementedError(
+            f"sort / argsort: no sorting kernel for dtype {bd.dtype}")
+    out_dtype = np.dtype(np.int64) if want_index else bd.dtype
+    if nd == 2:
+        out_bd = self.new_result(bd.shape, out_dtype, bd.divisions)
+        hooks.sort_lines(bd, self, out_bd, want_index)
+        return out_bd
+
+    W, me = self.world, self.rank
+    core = self.core_box(bd, me)
+    start = 0 if core is None else int(core[0, 0])
+    keys, gidx = hooks.sort_run(hooks.local_run(bd, self), None, start, True,
+                                want_index)
+    n_loc = int(keys.shape[0])
+    # W-1 regular samples per rank; a rank with no data contributes none
+    pick = [(j * n_loc) // W for j in range(1, W)] if n_loc else []
+    mine = keys[pick].cpu().numpy() if pick else \
+        np.empty(0, dtype=keys.cpu().numpy().dtype)
+    npdt = mine.dtype
+    have = [int(c) for c in self.backend.allgather_scalars(
+        np.int64(mine.size), np.int64)]
+    samples = []
+    for j in range(W - 1):      # allgather_scalars is the portable collective
+        col = self.backend.allgather_scalars(
+            mine[j] if mine.size else npdt.type(0), npdt)
+        samples.extend(col[r] for r in range(W) if have[r])
+    samples = np.sort(np.asarray(samples, dtype=npdt), kind="stable")
+    splitters = samples[[(j * samples.size) // W for j in range(1, W)]] \
+        if samples.size else samples
+    cuts = [0] + [int(c) for c in hooks.sort_bounds(keys, splitters)]
+    cuts += [n_loc] * (W + 1 - len(cuts))
+    # counts[r][s] = keys rank r sends to rank s
+    counts = np.zeros((W, W), dtype=np.int64)
+    for s in range(W):
+        col = self.backend.allgather_scalars(
+            np.int64(cuts[s + 1] - cuts[s]), np.int64)
+        counts[:, s] = [int(c) for c in col]
+
+    def swap(t, dtype):
+        sends = [(s, t[cuts[s]:cuts[s + 1]].contiguous()) for s in range(W)
+                 if s != me and counts[me, s]]
+        recvs = [(r, self.backend.new_message_buffer((int(counts[r, me]),),
+                                                     dtype))
+                 for r in range(W) if r != me and counts[r, me]]
+        if sends or recvs:
+            self.backend.exchange(sends, recvs)
+        got = dict(recvs)
+        got[me] = t[cuts[me]:cuts[me + 1]]
+        import torch
+        return torch.cat([got[r] for r in range(W) if r in got
+                          and got[r].shape[0]] or [t[:0]])
+
+    rkeys = swap(keys, bd.dtype)
+    ridx = swap(gidx, np.dtype(np.int64)) if want_index else None
+    skeys, sidx = hooks.sort_run(rkeys, ridx, 0, not want_index, want_index)
+
+    total = counts.sum(axis=0)
+    ends = np.cumsum(total)
+    boxes = [None if total[r] == 0 else
+             np.array([[int(ends[r] - total[r])], [int(ends[r]) - 1]])
+             for r in range(W)]
+    out_bd = self.new_result(bd.shape, out_dtype,
+                             divisions_from_boxes(boxes, 1))
+    if total[me]:
+        self.backend.write_local_dense(out_bd, self,
+                                       sidx if want_index else skeys)
+    self.backend.free_temps()
+    return out_bd
+
+
+Runtime.sort_op = sort_op
