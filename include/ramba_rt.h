@@ -28,6 +28,8 @@
  *   rt_sort_lines     — stable sort of many short lines (sort / argsort
  *                       along an axis; no reference counterpart)
  *   rt_sort_bounds    — lower bounds of splitter keys in a sorted run
+ *   rt_select_pass    — one counting pass of a radix select (median /
+ *                       percentile / quantile; no reference counterpart)
  *   rt_stream_sync /
  *   rt_device_sync    — worker-side completion (sync, ramba.py:9843)
  *   rt_event_*        — hot-loop timing (add_time, ramba.py:945-1022)
@@ -440,6 +442,68 @@ int rt_sort_bounds(uintptr_t stream, const void *run, int64_t n, int dtype,
 int rt_sort_geometry(int *block, int *keys_per_lane, int *grid_cap,
                      int *wave_max, int64_t *lines_per_launch,
                      int64_t *line_max);
+
+/* order statistics — one MSD pass of a radix select (numpy.median /
+ * percentile / quantile; the reference has none).  The order is that of
+ * ramba_sortkey.h: digits are SELECT_DIGIT_BITS = 8 bits of rt_sort_canon(raw
+ * bits), and a selected key is turned back into an element by
+ * rt_sort_decode, so no raw element is carried.
+ *
+ * rt_select_pass reads a strided box of 1..4 axes at `in + in_off`, addressed
+ * as rt_hist addresses its input (offset and strides in elements, any sign,
+ * zero allowed); dtype: any rt_dtype.
+ *   shift       the bit position of this pass's digit: a multiple of 8 with
+ *               shift + 8 <= the key width.
+ *   nq          1 <= nq <= nq_max (8) prefixes.
+ *   prefixes    host array of nq DISTINCT uint64 values: the key bits above
+ *               shift + 8 that are already decided, in place (every bit at or
+ *               below shift + 8 clear).  On the top pass shift + 8 is the key
+ *               width and the one prefix is 0.
+ *   counts      device int64[nq][256]; the kernel ADDS, the caller zeroes.
+ *               An element whose key matches prefix q above shift + 8 adds
+ *               one to counts[q][(key >> shift) & 255]; prefixes are
+ *               distinct, so at most one matches.
+ *   nan_count   device int64, may be NULL: for float dtypes the kernel adds
+ *               the number of elements whose key is all ones (NaN).  It looks
+ *               at every element, whatever the prefixes; not counted with
+ *               `canonical` set.
+ *   collect_buf device array of collect_cap keys (the unsigned type of the
+ *   collect_cap dtype's width), may be NULL; cursor: device uint64, zeroed by
+ *   cursor      the caller.  Every matching element's canonical key is
+ *               appended: a wave stages its matches in LDS (ballot, popcount,
+ *               rank among the matching lanes) and appends up to 256 at a
+ *               time with one atomic add on the cursor.  Nothing is written
+ *               at or past collect_cap; the cursor still counts what did not
+ *               fit.  The order of the collected keys is unspecified.
+ *   canonical   nonzero: `in` already holds canonical keys of the unsigned
+ *               type of dtype's width (a collect buffer), a dense 1-D run;
+ *               the transform is skipped.  dtype still names the element type
+ *               the keys came from, which fixes the key width, so the one
+ *               dtype table needs no unsigned codes.
+ * Counters: a private uint32[nq][256] LDS copy per wave of the 256-lane block
+ * (32 KB at nq = 8; collecting adds 256 keys of stage per wave, at most 8 KB),
+ * flushed with 64-bit atomic adds of the nonzero bins;
+ * at most grid_cap blocks run and no block counts more than 2^31 elements
+ * between flushes (longer boxes take several launches), both as rt_hist.
+ * When every active lane of a wave holds the same (prefix, digit), one lane
+ * adds the lane count; when none matches nothing is added.  Prefixes travel
+ * as kernel arguments.  16-byte loads under the rt_arg_flat_regime rule, else
+ * element loads.  counts and nan_count are exact integers, so every result is
+ * the same from run to run; no kernel waits for another block.
+ * Validated before any HIP call: nd, NULL shape / strides, extents, dtype,
+ * shift, nq, NULL / out-of-place / duplicate prefixes, collect_cap < 0, a
+ * collect buffer without a cursor, canonical with nd != 1 or a non-unit
+ * stride, NULL in / counts with work to do.  A zero extent returns 0 without
+ * launching.
+ * rt_select_geometry: the compiled-in constants (any pointer may be NULL);
+ * host arithmetic only. */
+int rt_select_pass(uintptr_t stream, const void *in, int64_t in_off, int nd,
+                   const int64_t *shape, const int64_t *strides, int dtype,
+                   int canonical, int shift, int nq, const uint64_t *prefixes,
+                   void *counts, void *nan_count, void *collect_buf,
+                   int64_t collect_cap, void *cursor);
+int rt_select_geometry(int *grid_cap, int *block, int *nq_max,
+                       int *digit_bits);
 
 int rt_stream_sync(uintptr_t stream);
 int rt_device_sync(void);

@@ -1,4 +1,4 @@
-/* ramba_sortkey — the order of sort / argsort.
+/* ramba_sortkey — the order of sort / argsort and of the order statistics.
  *
  * ONE function decides every digit and every comparison: the radix passes of
  * rt_sort, the compare-exchanges of rt_sort_lines and the binary search of
@@ -63,6 +63,27 @@ rt_sort_canon(typename rt_sort_key<T>::U u) {
         return (u & sign) ? (U)~u : (U)(u | sign);
     }
     return rt_sort_key<T>::SGN ? (U)(u ^ sign) : u;
+}
+
+/* The inverse: the raw bits of the element that a canonical key stands for.
+ * Exact for integers and for every float but the two the key does not tell
+ * apart: a zero comes back as +0.0 and a NaN as the one quiet NaN with a
+ * clear sign and an empty payload.  rt_sort_canon(rt_sort_decode(k)) == k for
+ * every key that rt_sort_canon can return.  Selection (rt_select_pass) finds
+ * an order statistic as a key and decodes it here, so no raw element is ever
+ * carried. */
+template <typename T>
+RT_SORT_HD typename rt_sort_key<T>::U
+rt_sort_decode(typename rt_sort_key<T>::U k) {
+    typedef typename rt_sort_key<T>::U U;
+    const U sign = (U)((U)1 << (8 * sizeof(U) - 1));
+    if (rt_sort_key<T>::FLT) {
+        const int mbits = sizeof(U) == 4 ? 23 : 52;
+        if (k == (U)~(U)0)                      /* NaN: exponent | quiet bit */
+            return (U)((U)(sign - 1) >> (mbits - 1) << (mbits - 1));
+        return (k & sign) ? (U)(k ^ sign) : (U)~k;
+    }
+    return rt_sort_key<T>::SGN ? (U)(k ^ sign) : k;
 }
 
 #endif /* RAMBA_SORTKEY_H */

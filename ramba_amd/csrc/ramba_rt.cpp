@@ -3356,6 +3356,46 @@ int hist_launch_k(uintptr_t stream, const T *src, HistArgs a, int64_t nunits,
     return 0;
 }
 
+// The walk of a box in load units, shared with rt_select_pass: fills the
+// geometry fields of `a` (nd, shp, str, tail0, tailn), sets *nunits and
+// returns whether the box takes 16-byte loads.
+bool hist_box_args(const void *in, int64_t in_off, int nd,
+                   const int64_t *shape, const int64_t *strides, int es,
+                   int64_t n, HistArgs *out, int64_t *nunits_out) {
+    HistArgs &a = *out;
+    const bool vec = arg_flat_vec(in, in_off, nd, shape, strides, es);
+    const int64_t per = vec ? 16 / (int64_t)es : 1;
+    a.tail0 = a.tailn = 0;
+    for (int d = 0; d < 4; ++d) {
+        const int s = d - (4 - nd);
+        a.shp[d] = s >= 0 ? shape[s] : 1;
+        a.str[d] = s >= 0 ? strides[s] : 0;
+        if (vec && d < 3) a.str[d] /= per;
+    }
+    int64_t nunits = n;
+    if (vec) {
+        a.tail0 = (a.shp[3] / per) * per;
+        a.tailn = a.shp[3] - a.tail0;     // nonzero only when nd == 1
+        a.shp[3] /= per;
+        nunits = n / shape[nd - 1] * a.shp[3];
+    }
+    // merge every axis that is dense over its inner neighbour, so a
+    // contiguous N-D box walks as one axis, with no division per unit
+    int k = 3;
+    for (int d = 2; d >= 4 - nd; --d) {
+        if (a.str[d] == a.shp[k] * a.str[k]) {
+            a.shp[k] *= a.shp[d];
+        } else {
+            --k;
+            a.shp[k] = a.shp[d];
+            a.str[k] = a.str[d];
+        }
+    }
+    a.nd = 4 - k;
+    *nunits_out = nunits;
+    return vec;
+}
+
 template <typename T, typename L>
 int hist_launch_l(uintptr_t stream, const T *src, const HistArgs &a,
                   int64_t nunits, int mode, const void *edges,
@@ -3421,41 +3461,13 @@ extern "C" int rt_hist(uintptr_t stream, const void *in, int64_t in_off,
 
     return dtype_dispatch<7>(who, dtype, [&](auto t) {
         using T = decltype(t);
-        const bool vec =
-            arg_flat_vec(in, in_off, nd, shape, strides, sizeof(T));
-        const int64_t per = vec ? 16 / (int64_t)sizeof(T) : 1;
         HistArgs a;
-        a.nd = nd;
+        int64_t nunits;
+        const bool vec = hist_box_args(in, in_off, nd, shape, strides,
+                                       sizeof(T), n, &a, &nunits);
         a.nbins = nbins;
         a.regime = hist_regime(nbins);
         a.stage_edges = mode != HIST_INDEX && nbins + 1 <= HIST_EDGES_LDS_MAX;
-        a.tail0 = a.tailn = 0;
-        for (int d = 0; d < 4; ++d) {
-            const int s = d - (4 - nd);
-            a.shp[d] = s >= 0 ? shape[s] : 1;
-            a.str[d] = s >= 0 ? strides[s] : 0;
-            if (vec && d < 3) a.str[d] /= per;
-        }
-        int64_t nunits = n;
-        if (vec) {
-            a.tail0 = (a.shp[3] / per) * per;
-            a.tailn = a.shp[3] - a.tail0;     // nonzero only when nd == 1
-            a.shp[3] /= per;
-            nunits = n / shape[nd - 1] * a.shp[3];
-        }
-        // merge every axis that is dense over its inner neighbour, so a
-        // contiguous N-D box walks as one axis, with no division per unit
-        int k = 3;
-        for (int d = 2; d >= 4 - nd; --d) {
-            if (a.str[d] == a.shp[k] * a.str[k]) {
-                a.shp[k] *= a.shp[d];
-            } else {
-                --k;
-                a.shp[k] = a.shp[d];
-                a.str[k] = a.str[d];
-            }
-        }
-        a.nd = 4 - k;
         const T *src = static_cast<const T *>(in) + in_off;
         if (vec)
             return hist_launch_l<T, uint4>(stream, src, a, nunits, mode, edges,
@@ -4088,5 +4100,291 @@ extern "C" int rt_sort_bounds(uintptr_t stream, const void *run, int64_t n,
             static_cast<const SortU<T> *>(splitters), m,
             static_cast<int64_t *>(bounds));
         return launched(who);
+    });
+}
+
+// ---------------------------------------------------------------------------
+// Order statistics (numpy.median / percentile / quantile; the reference has
+// none): rt_select_pass, one MSD pass of a radix select over the canonical
+// key of ramba_sortkey.h.
+//
+// A selection only has to know how many keys fall in each digit bin below
+// the prefixes already decided, so a pass is a keyed count that moves no
+// data: every element's key is compared with up to SELECT_NQ_MAX distinct
+// prefixes (kernel arguments, copied into LDS once per block so that they
+// hold no scalar registers through the loop) and the one it matches, if
+// any, gets a count in that prefix's 256 bins.  The box is
+// walked as rt_hist walks it (hist_box_args, hist_unit_off: 16-byte loads
+// under the rt_arg_flat rule, two loads in flight per lane, the capped grid,
+// at most 2^31 elements per block and launch).
+//
+// Counters: uint32[nq][256] in LDS per wave of the 256-lane block (32 KB at
+// nq = 8), summed and flushed with 64-bit atomic adds of the nonzero bins.
+// The top pass of real float data is one hot bin, so the wave rule of
+// rt_hist applies: when every active lane holds the same (prefix, digit),
+// or none matches, one lane adds the lane count (or nothing is added).
+// After the first narrowing almost no lane matches and the pass is a
+// streaming read.
+//
+// Collect: with a buffer, each wave stages the keys that matched in its own
+// LDS (ballot, popcount, the lane's rank among the matching lanes) and
+// appends SELECT_STAGE of them at a time with one atomic add on the cursor;
+// scattered matches would otherwise queue on that one address.  A slot at
+// or past collect_cap is not written.  Later passes read that buffer with
+// CANON set, which skips the transform.
+// Everything written is an integer count or a key whose position does not
+// matter, so results are the same from run to run.
+// ---------------------------------------------------------------------------
+
+namespace {
+
+enum { SELECT_NQ_MAX = 8, SELECT_DIGIT_BITS = 8, SELECT_STAGE = 256 };
+
+struct SelectArgs {
+    HistArgs box;                    // the walk; the binning fields are unused
+    uint64_t pre[SELECT_NQ_MAX];     // the decided high bits, in place
+    uint64_t mask;                   // the key bits above shift + 8
+    int64_t cap;                     // collect capacity, in keys
+    int shift, nq;
+};
+
+// the rt_hist wave rule on a wave's LDS copy; b < 0: nothing to count
+__device__ __forceinline__ void select_count(uint32_t *cnt, int b) {
+    const uint64_t act = __ballot(1);
+    const int b0 = __builtin_amdgcn_readfirstlane(b);
+    if (__ballot(b == b0) == act) {
+        if (b0 >= 0 && (int)__lane_id() == __ffsll((long long)act) - 1)
+            atomicAdd(&cnt[b0], (uint32_t)__popcll(act));
+        return;
+    }
+    if (b >= 0) atomicAdd(&cnt[b], 1u);
+}
+
+// A wave's staged keys go to the collect buffer with ONE atomic add on the
+// cursor; run by whichever lanes of the wave are active.  `stage` and
+// `staged` are the wave's own LDS, volatile so that the accesses of one wave,
+// which the hardware performs in order, also stay in program order.
+template <typename U>
+__device__ __forceinline__ void select_flush(
+    volatile U *stage, volatile int *staged, int64_t cap,
+    U *__restrict__ collect, unsigned long long *__restrict__ cursor) {
+    const uint64_t act = __ballot(1);
+    const int lane = (int)__lane_id();
+    const int n = *staged;
+    int64_t base = 0;
+    if (lane == __ffsll((long long)act) - 1)
+        base = (int64_t)atomicAdd(cursor, (unsigned long long)n);
+    base = gemm_uniform(base);                  // the first active lane's
+    for (int i = __popcll(act & (((uint64_t)1 << lane) - 1)); i < n;
+         i += __popcll(act))
+        if (base + i < cap) collect[base + i] = stage[i];
+    if (lane == __ffsll((long long)act) - 1) *staged = 0;
+}
+
+template <typename T, typename L, bool CANON>
+__device__ __forceinline__ void select_unit(
+    const L &unit, const SelectArgs &s, const uint64_t *pre, uint32_t *cnt,
+    uint32_t &nnan, volatile typename rt_sort_key<T>::U *stage,
+    volatile int *staged, typename rt_sort_key<T>::U *__restrict__ collect,
+    unsigned long long *__restrict__ cursor) {
+    typedef typename rt_sort_key<T>::U U;
+    constexpr int PER = sizeof(L) / sizeof(U);
+    U e[PER];
+    __builtin_memcpy(e, &unit, sizeof(L));
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+        const U key = CANON ? e[j] : rt_sort_canon<T>(e[j]);
+        if (rt_sort_key<T>::FLT && !CANON) nnan += key == (U) ~(U)0;
+        const uint64_t hi = (uint64_t)key & s.mask;
+        int q = -1;
+#pragma nounroll
+        for (int k = 0; k < s.nq; ++k)
+            if (hi == pre[k]) q = k;
+        select_count(cnt, q < 0 ? -1
+                                : q * 256 + (int)(((uint64_t)key >> s.shift)
+                                                  & 255));
+        if (collect) {
+            const uint64_t m = __ballot(q >= 0);
+            if (m) {
+                const int add = __popcll(m);
+                if (*staged + add > SELECT_STAGE)
+                    select_flush<U>(stage, staged, s.cap, collect, cursor);
+                const int at = *staged;
+                if (q >= 0)
+                    stage[at + __popcll(m & (((uint64_t)1 << __lane_id())
+                                             - 1))] = key;
+                if ((int)__lane_id() == __ffsll((long long)m) - 1)
+                    *staged = at + add;
+            }
+        }
+    }
+}
+
+// L = uint4 when the box takes 16-byte loads, else one key
+template <typename T, typename L, bool CANON>
+__global__ __launch_bounds__(256) void select_kernel(
+    const typename rt_sort_key<T>::U *__restrict__ in, SelectArgs s,
+    unsigned long long *__restrict__ counts,
+    unsigned long long *__restrict__ nan_count,
+    typename rt_sort_key<T>::U *__restrict__ collect,
+    unsigned long long *__restrict__ cursor) {
+    typedef typename rt_sort_key<T>::U U;
+    extern __shared__ __align__(16) unsigned char select_lds[];
+    // LDS: the prefixes (read per element, so that they hold no scalar
+    // registers through the loop), then the four waves' counters
+    uint64_t *pre = reinterpret_cast<uint64_t *>(select_lds);
+    uint32_t *all = reinterpret_cast<uint32_t *>(pre + SELECT_NQ_MAX);
+    const int tid = threadIdx.x;
+    const int nb = s.nq * 256;
+    // when collecting: each wave's count of staged keys, and its stage
+    int *nst = reinterpret_cast<int *>(all + 4 * nb);
+    volatile int *staged = nst + (tid >> 6);
+    volatile U *stage = reinterpret_cast<U *>(nst + 4)
+                        + (tid >> 6) * SELECT_STAGE;
+    if (tid < SELECT_NQ_MAX) pre[tid] = s.pre[tid];
+    if (collect && tid < 4) nst[tid] = 0;
+    for (int k = tid; k < 4 * nb; k += 256) all[k] = 0u;
+    __syncthreads();
+    uint32_t *cnt = all + (tid >> 6) * nb;
+    uint32_t nnan = 0;
+
+    const HistArgs &a = s.box;
+    const L *src = reinterpret_cast<const L *>(in);
+    const int64_t S = (int64_t)gridDim.x * 256;
+    int64_t u = a.u0 + (int64_t)blockIdx.x * 256 + tid;
+    for (; u + S < a.u1; u += 2 * S) {
+        const L x0 = src[hist_unit_off(a, u)];
+        const L x1 = src[hist_unit_off(a, u + S)];
+        select_unit<T, L, CANON>(x0, s, pre, cnt, nnan, stage, staged, collect,
+                                 cursor);
+        select_unit<T, L, CANON>(x1, s, pre, cnt, nnan, stage, staged, collect,
+                                 cursor);
+    }
+    if (u < a.u1) {
+        const L x0 = src[hist_unit_off(a, u)];
+        select_unit<T, L, CANON>(x0, s, pre, cnt, nnan, stage, staged, collect,
+                                 cursor);
+    }
+    const int64_t t = (int64_t)blockIdx.x * 256 + tid;
+    if (a.u0 == 0 && t < a.tailn)
+        select_unit<T, U, CANON>(in[a.tail0 + t], s, pre, cnt, nnan, stage,
+                                 staged, collect, cursor);
+    if (collect && *staged)         // the whole wave is here again
+        select_flush<U>(stage, staged, s.cap, collect, cursor);
+    if (rt_sort_key<T>::FLT && !CANON && nnan && nan_count)
+        atomicAdd(nan_count, (unsigned long long)nnan);
+
+    __syncthreads();
+    for (int b = tid; b < nb; b += 256) {
+        const uint32_t v = all[b] + all[nb + b] + all[2 * nb + b]
+                           + all[3 * nb + b];
+        if (v) atomicAdd(&counts[b], (unsigned long long)v);
+    }
+}
+
+template <typename T, typename L, bool CANON>
+int select_launch(uintptr_t stream, const void *src, SelectArgs s,
+                  int64_t nunits, void *counts, void *nan_count,
+                  void *collect, void *cursor) {
+    typedef typename rt_sort_key<T>::U U;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const size_t lds = SELECT_NQ_MAX * sizeof(uint64_t)
+                       + (size_t)4 * s.nq * 256 * sizeof(uint32_t)
+                       + (collect ? 4 * sizeof(int)
+                                        + 4 * SELECT_STAGE * sizeof(U)
+                                  : 0);
+    // as rt_hist: a launch covers at most HIST_LAUNCH_TRIPS units per lane
+    // of the capped grid, and the 1-D scalar tail rides on the first one
+    const int64_t span = (int64_t)HIST_GRID_CAP * 256 * HIST_LAUNCH_TRIPS;
+    for (int64_t u0 = 0; u0 == 0 || u0 < nunits; u0 += span) {
+        s.box.u0 = u0;
+        s.box.u1 = nunits - u0 < span ? nunits : u0 + span;
+        int64_t blocks = (s.box.u1 - s.box.u0 + 255) / 256;
+        if (blocks > HIST_GRID_CAP) blocks = HIST_GRID_CAP;
+        if (blocks < 1) blocks = 1;
+        hipLaunchKernelGGL((select_kernel<T, L, CANON>),
+                           dim3((unsigned)blocks), dim3(256), lds, st,
+                           static_cast<const U *>(src), s,
+                           static_cast<unsigned long long *>(counts),
+                           static_cast<unsigned long long *>(nan_count),
+                           static_cast<U *>(collect),
+                           static_cast<unsigned long long *>(cursor));
+        if (launched("rt_select_pass")) return 1;
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int rt_select_geometry(int *grid_cap, int *block, int *nq_max,
+                                  int *digit_bits) {
+    if (grid_cap) *grid_cap = HIST_GRID_CAP;
+    if (block) *block = 256;
+    if (nq_max) *nq_max = SELECT_NQ_MAX;
+    if (digit_bits) *digit_bits = SELECT_DIGIT_BITS;
+    return 0;
+}
+
+extern "C" int rt_select_pass(uintptr_t stream, const void *in,
+                              int64_t in_off, int nd, const int64_t *shape,
+                              const int64_t *strides, int dtype,
+                              int canonical, int shift, int nq,
+                              const uint64_t *prefixes, void *counts,
+                              void *nan_count, void *collect_buf,
+                              int64_t collect_cap, void *cursor) {
+    const char *who = "rt_select_pass";
+    int64_t n;
+    if (box_extents(who, nd, 1, shape, strides, strides, &n)) return 1;
+    if (dtype < RT_F64 || dtype > RT_U8) return fail(who, "bad dtype");
+    const int width = 8 * dtype_size(dtype);
+    if (shift < 0 || shift % SELECT_DIGIT_BITS
+        || shift + SELECT_DIGIT_BITS > width)
+        return fail(who, "bad shift");
+    if (nq < 1 || nq > SELECT_NQ_MAX) return fail(who, "nq out of range");
+    if (!prefixes) return fail(who, "NULL prefixes");
+    const int top = shift + SELECT_DIGIT_BITS;      // bits below: undecided
+    const uint64_t keymask = width == 64 ? ~(uint64_t)0
+                                         : ((uint64_t)1 << width) - 1;
+    const uint64_t mask = top >= 64 ? 0 : keymask >> top << top;
+    for (int q = 0; q < nq; ++q) {
+        if (prefixes[q] & ~mask)
+            return fail(who, "prefix has bits outside the decided digits");
+        for (int p = 0; p < q; ++p)
+            if (prefixes[p] == prefixes[q])
+                return fail(who, "duplicate prefix");
+    }
+    if (collect_cap < 0) return fail(who, "negative collect_cap");
+    if (collect_buf && !cursor)
+        return fail(who, "collect buffer without a cursor");
+    if (canonical && (nd != 1 || strides[0] != 1))
+        return fail(who, "canonical input must be a dense 1-D run");
+    if (n == 0) return 0;
+    if (!in) return fail(who, "NULL in");
+    if (!counts) return fail(who, "NULL counts");
+
+    return dtype_dispatch<7>(who, dtype, [&](auto t) {
+        using T = decltype(t);
+        SelectArgs s;
+        int64_t nunits;
+        const bool vec = hist_box_args(in, in_off, nd, shape, strides,
+                                       sizeof(T), n, &s.box, &nunits);
+        s.box.nbins = 0, s.box.regime = 0, s.box.stage_edges = 0;
+        for (int q = 0; q < SELECT_NQ_MAX; ++q)
+            s.pre[q] = q < nq ? prefixes[q] : 0;
+        s.mask = mask, s.cap = collect_cap, s.shift = shift, s.nq = nq;
+        const void *src = static_cast<const T *>(in) + in_off;
+        if (canonical)
+            return vec ? select_launch<T, uint4, true>(
+                             stream, src, s, nunits, counts, nan_count,
+                             collect_buf, cursor)
+                       : select_launch<T, typename rt_sort_key<T>::U, true>(
+                             stream, src, s, nunits, counts, nan_count,
+                             collect_buf, cursor);
+        return vec ? select_launch<T, uint4, false>(
+                         stream, src, s, nunits, counts, nan_count,
+                         collect_buf, cursor)
+                   : select_launch<T, typename rt_sort_key<T>::U, false>(
+                         stream, src, s, nunits, counts, nan_count,
+                         collect_buf, cursor);
     });
 }

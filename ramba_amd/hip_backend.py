@@ -106,6 +106,10 @@ _RT_ABI = {
     "rt_sort_geometry": (_int, [ctypes.POINTER(_int), ctypes.POINTER(_int),
                                 ctypes.POINTER(_int), ctypes.POINTER(_int),
                                 _p64, _p64]),
+    "rt_select_pass": (_int, [_sz, _vp, _i64, _int, _p64, _p64, _int, _int,
+                              _int, _int, ctypes.POINTER(ctypes.c_uint64),
+                              _vp, _vp, _vp, _i64, _vp]),
+    "rt_select_geometry": (_int, [ctypes.POINTER(_int)] * 4),
     "rt_stream_sync": (_int, [_sz]),
     "rt_device_sync": (_int, []),
     "rt_event_create": (_int, [_pvp]),
@@ -162,6 +166,14 @@ def sort_geometry(lib):
             "tile": blk.value * kpl.value, "grid_cap": cap.value,
             "wave_max": wmax.value, "lines_per_launch": lpl.value,
             "line_max": {1 << k: int(lmax[k]) for k in range(4)}}
+
+
+def select_geometry(lib):
+    """rt_select_geometry as a dict (host arithmetic; needs no GPU)."""
+    vals = [ctypes.c_int() for _ in range(4)]
+    lib.rt_select_geometry(*[ctypes.byref(v) for v in vals])
+    return dict(zip(("grid_cap", "block", "nq_max", "digit_bits"),
+                    (v.value for v in vals)))
 
 
 def _hb_arg_chunks(nd, axis, nout, K):
@@ -1211,6 +1223,59 @@ class HipBackend:
             edt, int(nbins), ctypes.c_void_p(counts.data_ptr()),
             ctypes.c_void_p(bad.data_ptr())), "rt_hist")
         return counts, bad
+
+    # -- median / percentile / quantile (runtime.select_op) -------------------
+    #
+    # The hook of ramba_amd/selection.py on rt_select_pass.  The operand is
+    # read in place through the view's strides; counts, NaN count and cursor
+    # share one zeroed device tensor; collected keys stay on the device.
+
+    select_dtypes = frozenset(RT_DTYPE)  # select_op refuses any other, by name
+
+    def select_geometry(self):
+        """The compiled-in constants of rt_select_pass, by name."""
+        return select_geometry(self.lib)
+
+    def select_pass(self, source, shift, prefixes, collect):
+        from .selection import KeySource
+        torch = self.torch
+        nq = len(prefixes)
+        work = torch.zeros(nq * 256 + 2, dtype=torch.int64, device="cuda")
+        if isinstance(source, KeySource):
+            dtype, canonical = source.dtype, 1
+            base, off0 = source.keys, 0
+            shape, strides = (int(source.keys.numel()),), (1,)
+        else:
+            bd, rt = source.bd, source.rt
+            dtype, canonical = np.dtype(bd.dtype), 0
+            d_, _, cstrides, pads = rt.shard_geometry(bd)
+            off0, strides = source.view.operand_addressing(
+                source.lb[0], cstrides, d_[0], pads)
+            shape = box_shape(source.lb)
+            base = self._cont(bd)
+        buf = None
+        if collect is not None:
+            buf = torch.empty(
+                int(collect), device="cuda",
+                dtype={1: torch.uint8, 2: torch.int16, 4: torch.int32,
+                       8: torch.int64}[dtype.itemsize])
+        ptr = work.data_ptr()
+        self._check(self.lib.rt_select_pass(
+            self._stream(), ctypes.c_void_p(base.data_ptr()), int(off0),
+            len(shape), _i64arr(shape), _i64arr(strides),
+            RT_DTYPE[str(dtype)], canonical, int(shift), nq,
+            (ctypes.c_uint64 * nq)(*prefixes), ctypes.c_void_p(ptr),
+            ctypes.c_void_p(ptr + 8 * nq * 256),
+            # a capacity of 0 (no candidate in this rank's box) gives a NULL
+            # buffer: nothing is gathered and the KeySource below is empty,
+            # so the later passes over it launch nothing
+            ctypes.c_void_p(buf.data_ptr()) if buf is not None else None,
+            int(collect or 0),
+            ctypes.c_void_p(ptr + 8 * (nq * 256 + 1))
+            if buf is not None else None),
+            "rt_select_pass")
+        return (work[:nq * 256].view(nq, 256), work[nq * 256:nq * 256 + 1],
+                KeySource(buf, dtype) if buf is not None else None)
 
     # -- sort / argsort (runtime.sort_op) -------------------------------------
     #

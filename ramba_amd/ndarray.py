@@ -9,6 +9,7 @@ elementwise / reduction op records IR into the current fused group via
 
 import numbers
 import operator
+import warnings
 
 import numpy as np
 
@@ -1572,6 +1573,296 @@ ndarray._ARRAY_FUNC.update({
         sort(a, axis=axis, kind=kind, order=order),
     "argsort": lambda a, axis=-1, kind=None, order=None, **kw:
         argsort(a, axis=axis, kind=kind, order=order),
+})
+
+
+# -- median / percentile / quantile and their nan variants.  axis=None runs
+#    on runtime.select_op, a radix select that moves no data: the wanted
+#    ranks go in, canonical keys come back and are decoded on the host, and
+#    the few statistics are combined there with NumPy's own operations in
+#    NumPy's own dtypes (numpy.lib._function_base_impl: _quantile, _lerp,
+#    _median), so results are NumPy's bit for bit.  A zero comes back as
+#    +0.0 and a NaN as the default NaN: numpy.partition does not define
+#    which zero or which payload reaches position k.  Sync points.  Along
+#    an axis (the plain functions only) the lines are sorted with `sort`, the
+#    statistics are affine slices of the sorted array, and the same
+#    arithmetic runs as fused elementwise ops; the result is a ramba array. -
+
+_OS_METHODS = ("linear", "lower", "higher", "nearest", "midpoint")
+
+
+def _os_lerp(a, b, t):
+    """NumPy's _lerp: a + (b - a) * t, from b's side where t >= 0.5."""
+    diff = np.subtract(b, a)
+    r = np.asanyarray(np.add(a, diff * t))
+    np.subtract(b, diff * (1 - t), out=r, where=t >= 0.5, casting="unsafe",
+                dtype=type(r.dtype))
+    return r[()] if r.ndim == 0 else r
+
+
+def _os_plan(m, quant, method, floating):
+    """NumPy's _quantile up to the partition, for a line of m elements:
+    (ranks, gamma).  gamma None: the result is the ranks' elements; else
+    the first half of ranks are the lower neighbours, the second the upper,
+    and gamma, in the dtype NumPy gives it, interpolates."""
+    at = (m - 1) * quant
+    vi = np.asanyarray({
+        "linear": lambda: at,
+        "lower": lambda: np.floor(at).astype(np.intp),
+        "higher": lambda: np.ceil(at).astype(np.intp),
+        "nearest": lambda: np.around(at).astype(np.intp),
+        "midpoint": lambda: 0.5 * (np.floor(at) + np.ceil(at)),
+    }[method]())
+    if np.issubdtype(vi.dtype, np.integer):
+        return [int(i) % m for i in vi.ravel()], None
+    prev = np.asanyarray(np.floor(vi))
+    nxt = np.asanyarray(prev + 1)
+    for where, to in ((vi >= m - 1, m - 1), (vi < 0, 0)):
+        prev[where] = to
+        nxt[where] = to
+    if floating:
+        prev[np.isnan(vi)] = nxt[np.isnan(vi)] = m - 1
+    prev, nxt = prev.astype(np.intp), nxt.astype(np.intp)
+    gamma = np.asanyarray(vi - prev)
+    if method == "midpoint":
+        gamma = np.full(gamma.shape, 0.5)
+        np.copyto(gamma, 0., where=vi % 1 == 0, casting="unsafe")
+    gamma = np.asanyarray(gamma, dtype=vi.dtype)
+    return [int(i) for i in prev.ravel()] + [int(i) for i in nxt.ravel()], \
+        gamma
+
+
+def _os_combine(vals, gamma, shape):
+    """The result from the selected elements `vals` (1-D, the input dtype)."""
+    if gamma is None:
+        return vals.reshape(shape)[()]
+    k = vals.size // 2
+    return _os_lerp(vals[:k].reshape(shape)[()], vals[k:].reshape(shape)[()],
+                    gamma)
+
+
+def _os_args(name, a, axis, out, keepdims, weights=None, interpolation=None,
+             method="linear"):
+    """The refusals shared by the six functions; the input as a ramba array
+    of at most 4 axes."""
+    for what, given in (("out=", out is not None),
+                        ("keepdims=True", keepdims not in (False, np._NoValue)),
+                        ("weights=", weights is not None),
+                        ("interpolation=", interpolation is not None),
+                        ("an axis", axis is not None
+                         and name.startswith("nan"))):
+        if given:
+            raise NotImplementedError(f"{name}: {what} is not supported")
+    if method not in _OS_METHODS:
+        raise NotImplementedError(
+            f"{name}: method={method!r} is not supported; use one of "
+            f"{_OS_METHODS}")
+    if not isinstance(a, ndarray):
+        a = fromarray(np.asarray(a))
+    if a.dtype.kind not in "iuf" or a.dtype == np.float16:
+        raise NotImplementedError(
+            f"{name}: {a.dtype} input is not supported (integers and "
+            "float32 / float64 only)")
+    if a.ndim > 4:
+        raise NotImplementedError(
+            f"{name} supports arrays of up to 4 dimensions")
+    return a
+
+
+def _os_lines(a, axis):
+    """For a reduction along `axis` (an int or a tuple): `a` with those axes
+    moved last and folded, sorted along them, as (lines, length), and the
+    shape of the axes that stay.  None when every axis is reduced, which is
+    axis=None."""
+    axes = np.lib.array_utils.normalize_axis_tuple(axis, a.ndim)
+    if len(axes) == a.ndim:
+        return None
+    kept = tuple(i for i in range(a.ndim) if i not in axes)
+    if a.size == 0:     # nothing to sort: the caller takes NumPy's result
+        return None, tuple(a.shape[i] for i in kept)
+    m = a.transpose(kept + axes)
+    length = int(np.prod([a.shape[i] for i in axes]))
+    return sort(m.reshape((a.size // length, length)), axis=1), \
+        tuple(a.shape[i] for i in kept)
+
+
+def _os_nan_lines(s, r):
+    """NumPy's NaN check: a line whose last sorted element is a NaN gives
+    NaN."""
+    if s.dtype.kind != "f":
+        return r
+    return where(isnan(s[:, s.shape[1] - 1]), np.nan, r)
+
+
+def _os_axis_median(s, shape):
+    """NumPy's _median on the sorted lines `s`: the mean of the one or two
+    middle elements in the input dtype, float64 for integers."""
+    n = s.shape[1]
+    rdt = s.dtype if s.dtype.kind == "f" else np.dtype(np.float64)
+    r = s[:, (n - 1) // 2].astype(rdt)
+    if n % 2 == 0:
+        r = (r + s[:, n // 2].astype(rdt)) * 0.5
+    return _os_nan_lines(s, r).reshape(shape)
+
+
+def _os_axis_quantile(s, shape, quant, method):
+    """NumPy's _quantile on the sorted lines `s`: per q, the slices at its
+    ranks and _lerp between them, the side chosen on the host as gamma is
+    known there."""
+    ranks, gamma = _os_plan(s.shape[1], quant, method, s.dtype.kind == "f")
+    k = quant.size
+    if quant.ndim + len(shape) > 4:
+        raise NotImplementedError(
+            "a result of more than 4 dimensions is not supported")
+    outs = []
+    for i in range(k):
+        if gamma is None:
+            r = s[:, ranks[i]]
+        else:
+            t = gamma.ravel()[i]
+            rdt = np.result_type(s.dtype, gamma.dtype)
+            lo, hi = s[:, ranks[i]], s[:, ranks[k + i]]
+            diff = (hi - lo).astype(rdt)
+            if t >= 0.5:
+                r = hi.astype(rdt) - diff * float(1 - t)
+            else:
+                r = lo.astype(rdt) + diff * float(t)
+        outs.append(_os_nan_lines(s, r))
+    res = outs[0] if quant.ndim == 0 else stack(outs)
+    return res.reshape(quant.shape + shape)
+
+
+def _os_select(a, ranks, skipna):
+    """select_op on the flattened `a`: (the elements at `ranks` as a 1-D
+    host array of a's dtype, or None when a NaN decides; n; NaN count)."""
+    from .selection import decode
+    deferred.flush()
+    keys, n, c = deferred.get_runtime().select_op(a, ranks, skipna)
+    if keys is None:
+        return None, n, c
+    return np.array([decode(k, a.dtype) for k in keys], dtype=a.dtype), n, c
+
+
+def _os_all_nan():
+    warnings.warn("All-NaN slice encountered", RuntimeWarning, stacklevel=4)
+
+
+def _os_median(name, a, axis, out, overwrite_input, keepdims):
+    if not isinstance(a, ndarray):
+        kw = {} if keepdims is np._NoValue else {"keepdims": keepdims}
+        return getattr(np, name)(a, axis=axis, out=out,
+                                 overwrite_input=overwrite_input, **kw)
+    a = _os_args(name, a, axis, out, keepdims)
+    lines = _os_lines(a, axis) if axis is not None else None
+    if a.size == 0:     # NumPy's value and warnings for an empty input
+        r = getattr(np, name)(np.empty(a.shape, a.dtype), axis=axis)
+        return fromarray(r) if lines else r
+    if lines:
+        return _os_axis_median(*lines)
+    vals, n, c = _os_select(
+        a, lambda m: [m // 2 - 1, m // 2][m % 2:] if m else [],
+        name == "nanmedian")
+    if vals is None or vals.size == 0:
+        if vals is not None:
+            _os_all_nan()
+        return a.dtype.type(np.nan)
+    return np.mean(vals)
+
+
+def _os_quantile(name, a, q, axis, out, overwrite_input, method, keepdims,
+                 weights, interpolation):
+    if not isinstance(a, ndarray):
+        kw = {} if keepdims is np._NoValue else {"keepdims": keepdims}
+        return getattr(np, name)(
+            a, q.asarray() if isinstance(q, ndarray) else q, axis=axis,
+            out=out, overwrite_input=overwrite_input, method=method,
+            weights=weights, interpolation=interpolation, **kw)
+    a = _os_args(name, a, axis, out, keepdims, weights, interpolation, method)
+    if isinstance(q, ndarray):
+        q = q.asarray()
+    # NumPy's own conversion of q, which decides the dtype of the result
+    if name.endswith("percentile"):
+        quant = np.asanyarray(np.true_divide(
+            q, a.dtype.type(100) if a.dtype.kind == "f" else 100))
+    elif isinstance(q, (int, float)) and a.dtype.kind == "f":
+        quant = np.asanyarray(q, dtype=a.dtype)
+    else:
+        quant = np.asanyarray(q)
+    if quant.size and not (quant.min() >= 0 and quant.max() <= 1):
+        raise ValueError("Percentiles must be in the range [0, 100]"
+                         if name.endswith("percentile")
+                         else "Quantiles must be in the range [0, 1]")
+    lines = _os_lines(a, axis) if axis is not None else None
+    if a.size == 0 or quant.size == 0:
+        r = getattr(np, name)(np.empty(a.shape, a.dtype), q, axis=axis,
+                              method=method)
+        return fromarray(r) if lines else r
+    if lines:
+        return _os_axis_quantile(*lines, quant, method)
+    floating = a.dtype.kind == "f"
+    plan = {}
+
+    def ranks(m):
+        if m:
+            plan["ranks"], plan["gamma"] = _os_plan(m, quant, method,
+                                                    floating)
+        return plan.get("ranks", [])
+
+    vals, n, c = _os_select(a, ranks, name.startswith("nan"))
+    if vals is None:            # a NaN: NumPy returns the last sorted element
+        vals = np.full(len(ranks(n)), np.nan, dtype=a.dtype)
+        if quant.ndim == 0:
+            return vals[0]
+    elif vals.size == 0:
+        _os_all_nan()
+        return np.full(quant.shape, np.nan, dtype=a.dtype)[()]
+    return _os_combine(vals, plan["gamma"], quant.shape)
+
+
+def median(a, axis=None, out=None, overwrite_input=False, keepdims=False):
+    """numpy.median for ramba arrays.  Over all elements (axis=None) the one
+    or two middle elements are found with a radix select (no sort) and the
+    result is a NumPy scalar; along an axis or a tuple of axes the lines are
+    sorted and a ramba array comes back.  overwrite_input is accepted and
+    ignored; out= and keepdims=True are not supported."""
+    return _os_median("median", a, axis, out, overwrite_input, keepdims)
+
+
+def nanmedian(a, axis=None, out=None, overwrite_input=False,
+              keepdims=np._NoValue):
+    """numpy.nanmedian for ramba arrays, axis=None only."""
+    return _os_median("nanmedian", a, axis, out, overwrite_input, keepdims)
+
+
+def _os_public(name):
+    def f(a, q, axis=None, out=None, overwrite_input=False, method="linear",
+          keepdims=np._NoValue if name.startswith("nan") else False, *,
+          weights=None,
+          interpolation=None):
+        return _os_quantile(name, a, q, axis, out, overwrite_input, method,
+                            keepdims, weights, interpolation)
+    f.__name__ = name
+    f.__doc__ = (
+        f"numpy.{name} for ramba arrays: q a scalar or array-like, method "
+        f"one of {_OS_METHODS}.  Over all elements (axis=None): a radix "
+        "select, and NumPy's scalar or array of q's shape comes back.  "
+        + ("An axis, " if name.startswith("nan") else
+           "Along an axis or a tuple of axes: the lines are sorted and a "
+           "ramba array comes back.  ")
+        + "out=, keepdims=True, weights= and interpolation= are not "
+        "supported.")
+    return f
+
+
+percentile = _os_public("percentile")
+quantile = _os_public("quantile")
+nanpercentile = _os_public("nanpercentile")
+nanquantile = _os_public("nanquantile")
+
+ndarray._ARRAY_FUNC.update({
+    "median": median, "nanmedian": nanmedian, "percentile": percentile,
+    "quantile": quantile, "nanpercentile": nanpercentile,
+    "nanquantile": nanquantile,
 })
 
 

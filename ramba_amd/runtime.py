@@ -1585,3 +1585,129 @@ def sort_op(self, arr, axis, want_index):
 
 
 Runtime.sort_op = sort_op
+
+
+# ---------------------------------------------------------------------------
+# order statistics (numpy.median / percentile / quantile; the reference has
+# none): an MSD radix select over the canonical sort key, 8 bits a pass, top
+# digit first.  A pass only COUNTS, through the select_pass hook (ramba_amd/
+# selection.py): for every live prefix, the decided high bits of a wanted
+# statistic, how many keys fall in each of the 256 bins of the next digit.
+# Counts add over ranks, so the distributed form moves 2 KB of counts per
+# prefix and pass and no data.  Every rank then finds, with the same integer
+# arithmetic, the bin in which each wanted rank falls, subtracts the counts
+# below it and extends that statistic's prefix.  After the last digit the
+# prefix is the key, and the key decodes to the element.
+#
+# Equal prefixes are merged (the two ranks of a median part ways late), more
+# than NQ_MAX distinct ones take several launches of that pass.  Collect
+# rule, derived: a pass over the ORIGINAL data also gathers the keys that
+# match when all its prefixes fit one launch and the candidates entering it
+# (the chosen bins of the previous pass, summed over ranks) are at most n / 8:
+# the writes add at most an eighth to that pass's traffic, and every later
+# pass reads at most n / 8 keys.  Each rank sizes its buffer exactly, from
+# its own previous counts.
+#
+# backend.allreduce reduces one scalar, so the counts of a pass travel
+# pairwise with backend.exchange, as the partials of hist_op do, and are
+# summed on the host (integers: any order gives the same sums).
+# ---------------------------------------------------------------------------
+
+def _sum_over_ranks(self, h):
+    """The elementwise sum over ranks of the int64 host array `h`."""
+    if self.world == 1:
+        return h
+    import torch
+    mine = self.backend.new_message_buffer(h.shape, h.dtype)
+    mine.copy_(torch.from_numpy(h))
+    others = [r for r in range(self.world) if r != self.rank]
+    recvs = [(r, self.backend.new_message_buffer(h.shape, h.dtype))
+             for r in others]
+    self.backend.exchange([(r, mine) for r in others], recvs)
+    return h + sum(buf.cpu().numpy() for _, buf in recvs)
+
+
+def select_op(self, arr, ranks, skipna):
+    """(keys, n, c): the canonical keys (Python ints) of the ranks[i]-th
+    smallest elements of the flattened `arr`, its element count and its NaN
+    count, the same on every rank.  `ranks` are 0-based, or a function of
+    the number of ranked elements (n, or n - c with skipna: NaNs sort last)
+    that returns them.  keys is None when a NaN decides the result (c > 0
+    without skipna) and [] when nothing is ranked.  self.last_select says
+    what ran: launches, full_passes (over the original data), collected and
+    collect_pass (which pass gathered the candidates; 0 is the top)."""
+    from .selection import DIGIT_BITS, NQ_MAX, BoxSource, hooks_for
+    bd, v = arr.bdarray, arr.view
+    hooks = hooks_for(self.backend)
+    known = getattr(hooks, "select_dtypes", None)   # None: any NumPy dtype
+    if known is not None and str(np.dtype(bd.dtype)) not in known:
+        raise NotImplementedError(
+            f"median / percentile: no selection kernel for dtype {bd.dtype}")
+    width = 8 * np.dtype(bd.dtype).itemsize
+    n = int(arr.size)
+    lb = exec_boxes(v, bd.divisions)[self.rank]
+    source = BoxSource(bd, self, v, lb) if lb is not None else None
+    stats = self.last_select = {"launches": 0, "full_passes": 0,
+                                "collected": False, "collect_pass": None}
+    original, c, ks, prefixes = True, 0, None, [0]
+    cand, mine = n, {}      # candidates entering the pass: global, per prefix
+    for shift in range(width - DIGIT_BITS, -1, -DIGIT_BITS):
+        live = sorted(set(prefixes))
+        groups = [live[i:i + NQ_MAX] for i in range(0, len(live), NQ_MAX)]
+        collect = original and ks is not None and len(groups) == 1 \
+            and 8 * cand <= n
+        loc = np.zeros((len(live), 256), dtype=np.int64)
+        nan = 0
+        if source is not None:          # no box here: zeros
+            import torch
+            parts = []
+            for group in groups:
+                cap = sum(mine[p] for p in group) if collect else None
+                cnt, nn, got = hooks.select_pass(source, shift, group, cap)
+                parts += [cnt.reshape(-1), nn]
+                stats["launches"] += 1
+            # every group is launched; one read-back synchronises the pass
+            back = torch.cat(parts).cpu().numpy()
+            row = pos = 0
+            for group in groups:
+                loc[row:row + len(group)] = \
+                    back[pos:pos + 256 * len(group)].reshape(-1, 256)
+                row += len(group)
+                pos += 256 * len(group) + 1     # past that launch's NaN count
+            if ks is None:             # the top pass: one group, all elements
+                nan = int(back[-1])
+        stats["full_passes"] += original
+        tot = _sum_over_ranks(self, np.append(loc.reshape(-1), nan))
+        glob = tot[:-1].reshape(loc.shape)
+        if collect:
+            original, stats["collected"] = False, True
+            stats["collect_pass"] = (width - shift) // DIGIT_BITS - 1
+            if source is not None:
+                source = got
+        if ks is None:                  # the top pass: now the ranks are known
+            c = int(tot[-1])
+            if c and not skipna:
+                self.backend.free_temps()
+                return None, n, c
+            m = n - c if skipna else n
+            ks = [int(k) for k in (ranks(m) if callable(ranks) else ranks)]
+            if not ks:
+                self.backend.free_temps()
+                return [], n, c
+            assert all(0 <= k < m for k in ks), (ks, m)
+            prefixes = [0] * len(ks)
+        chosen = {}
+        for i, k in enumerate(ks):
+            row = live.index(prefixes[i])
+            cum = np.cumsum(glob[row])
+            b = int(np.searchsorted(cum, k, side="right"))
+            ks[i] = k - (int(cum[b - 1]) if b else 0)
+            prefixes[i] |= b << shift
+            chosen[prefixes[i]] = (int(glob[row, b]), int(loc[row, b]))
+        cand = sum(gl for gl, _ in chosen.values())
+        mine = {p: lo for p, (_, lo) in chosen.items()}
+    self.backend.free_temps()
+    return prefixes, n, c
+
+
+Runtime.select_op = select_op
