@@ -30,6 +30,11 @@
  *   rt_sort_bounds    — lower bounds of splitter keys in a sorted run
  *   rt_select_pass    — one counting pass of a radix select (median /
  *                       percentile / quantile; no reference counterpart)
+ *   rt_unique_count /
+ *   rt_unique_write   — run compaction of a sorted run (unique; no reference
+ *                       counterpart)
+ *   rt_searchsorted   — batched binary search behind an LDS fence
+ *                       (searchsorted; no reference counterpart)
  *   rt_stream_sync /
  *   rt_device_sync    — worker-side completion (sync, ramba.py:9843)
  *   rt_event_*        — hot-loop timing (add_time, ramba.py:945-1022)
@@ -504,6 +509,93 @@ int rt_select_pass(uintptr_t stream, const void *in, int64_t in_off, int nd,
                    int64_t collect_cap, void *cursor);
 int rt_select_geometry(int *grid_cap, int *block, int *nq_max,
                        int *digit_bits);
+
+/* unique — numpy.unique of a SORTED dense run (the reference has none): the
+ * run compaction that follows rt_sort.  keys: n raw keys of `dtype` (any
+ * rt_dtype) in the canonical order of ramba_sortkey.h, as rt_sort leaves
+ * them; pos: optionally the n int64 payloads that travelled with them (the
+ * global positions of a stable argsort).
+ *
+ * Head rule, the only test of equality: key i is a run head iff i == 0 or
+ * rt_sort_canon(key[i]) != rt_sort_canon(key[i-1]).  So -0.0 and +0.0 are one
+ * value and all NaNs are one value (NumPy's equal_nan=True), and a run's
+ * head is its first key in the stable order.
+ *
+ * Three launches and a small tail, none of which waits for another block, no
+ * atomics: every output is the same from run to run.
+ *   rt_unique_count   (1) at most grid_cap blocks, each over a contiguous
+ *       range of tiles of block x keys_per_lane keys; a lane owns
+ *       keys_per_lane CONSECUTIVE keys, read with 16-byte loads when the run
+ *       is 16-byte aligned and the tile whole (else by element), and
+ *       compares them in registers; the neighbour across a lane boundary
+ *       comes by shuffle, the one across a wave or tile boundary from a
+ *       second load.  Heads are counted by ballot and popcount; one int64 per
+ *       block goes to the scratch.  (2) one block scans the per-block counts.
+ *       The call synchronises the stream once and returns the number of
+ *       distinct values in *n_unique, so the caller can size the outputs.
+ *   rt_unique_write   (3) the same tiling re-flags the heads; a head's slot
+ *       u is the block's base from (2), plus the heads of the tiles before,
+ *       plus a 4-entry LDS scan over the waves, plus ballot and popcount
+ *       within the wave.  Must follow rt_unique_count on the same keys, n and
+ *       scratch.  The head at run position i writes
+ *           out_keys[u]   = key[i], the RAW bits: the zero sign and the NaN
+ *                           payload of the first occurrence survive;
+ *           out_first[u]  = pos[i], or i when pos is NULL;
+ *           out_counts[u] = i, and two trailing launches turn these starts
+ *                           in place into counts[u] = start[u+1] - start[u],
+ *                           with n closing the last run.
+ *       Each output may be NULL (not all three); a NULL output's stores, and
+ *       for out_counts the trailing launches, are skipped.  The call does not
+ *       synchronise.
+ * scratch: device memory, 16-byte aligned, at least rt_unique_scratch(n)
+ * bytes (a few KB: two int64 per block and grid_cap range edges).
+ * Validated before any HIP call: dtype, n < 0 or >= 2^40, NULL keys / scratch
+ * / n_unique with work to do, a misaligned or too small scratch, all three
+ * outputs NULL.  n == 0 returns 0 without launching (*n_unique = 0).
+ * rt_unique_scratch (-1 for a bad n) and rt_unique_geometry (the compiled-in
+ * constants; any pointer may be NULL) are host arithmetic only. */
+int rt_unique_count(uintptr_t stream, const void *keys, int64_t n, int dtype,
+                    void *scratch, int64_t scratch_bytes, int64_t *n_unique);
+int rt_unique_write(uintptr_t stream, const void *keys, const void *pos,
+                    int64_t n, int dtype, void *scratch, void *out_keys,
+                    void *out_first, void *out_counts);
+int64_t rt_unique_scratch(int64_t n);
+int rt_unique_geometry(int *block, int *keys_per_lane, int *grid_cap);
+
+/* searchsorted — numpy.searchsorted (the reference has none).  v: m keys of
+ * `dtype` (any rt_dtype), dense, sorted in the canonical order of
+ * ramba_sortkey.h (raw bits; the caller's promise, as NumPy's).  Needles: a
+ * strided box of 1..4 axes at `x + x_off`, same dtype, addressed as rt_hist
+ * addresses its input (offset and strides in elements, any sign, zero
+ * allowed).  out: dense C-order int64 over the box.  side 0 (left): the
+ * number of keys that sort strictly before the needle; side 1 (right): the
+ * number that do not sort after it.  Both in the canonical order: a NaN
+ * needle lands at the first NaN (left) or after the last (right), and -0.0
+ * and +0.0 are equal, as in NumPy.
+ * Every search runs a FIXED number of branch-free trips (set on the host
+ * from the sizes alone), so a wave does not diverge.  Two regimes by m:
+ *   LDS    m <= lds_max[key width]: every block stages all of v, as
+ *          canonical keys, in at most 64 KB of LDS (two blocks a CU) and
+ *          grid-strides over the needles; no probe leaves the CU.
+ *   FENCE  larger m: seg = ceil(m / fence); the block stages the keys v[0],
+ *          v[seg], v[2 seg], .. (at most `fence`, a power of two; real keys
+ *          only).  A needle searches the fence in LDS, log2(fence) trips,
+ *          and finishes in one segment of at most seg keys in global memory.
+ *          Exact for both sides and for duplicates that span fence entries
+ *          (the argument is in DESIGN.md section 4g).
+ * Needles take 16-byte loads under the rt_arg_flat_regime rule, else element
+ * loads; at most grid_cap blocks of `block` lanes run.
+ * Validated before any HIP call: nd, NULL shape / strides, extents, dtype,
+ * side, m < 0 or >= 2^40, NULL v with m > 0, NULL x / out with work to do.
+ * A zero extent returns 0 without launching; m == 0 writes zeros.
+ * rt_searchsorted_geometry: the compiled-in constants (lds_max: 4 values,
+ * for key widths 1, 2, 4 and 8 bytes; any pointer may be NULL); host
+ * arithmetic only. */
+int rt_searchsorted(uintptr_t stream, const void *v, int64_t m, const void *x,
+                    int64_t x_off, int nd, const int64_t *shape,
+                    const int64_t *strides, int dtype, int side, void *out);
+int rt_searchsorted_geometry(int *block, int *fence, int64_t *lds_max,
+                             int *grid_cap);
 
 int rt_stream_sync(uintptr_t stream);
 int rt_device_sync(void);

@@ -4388,3 +4388,559 @@ extern "C" int rt_select_pass(uintptr_t stream, const void *in,
                          collect_buf, cursor);
     });
 }
+
+// ---------------------------------------------------------------------------
+// unique (numpy.unique of a sorted run; the reference has none): the
+// rt_unique_* run compaction.  The input is what rt_sort leaves: a dense run
+// of raw keys in the canonical order of ramba_sortkey.h, optionally with the
+// int64 payloads that travelled with them.
+//
+// Head rule: key i is a run head iff i == 0 or rt_sort_canon(key[i]) !=
+// rt_sort_canon(key[i-1]).  Nothing else decides equality, so -0.0 and +0.0
+// are one value and all NaNs are one value; the head is the FIRST key of its
+// run and its raw bits are what is written.
+//
+// Tiling (both passes): a tile is UNIQ_BLOCK x UNIQ_KPL consecutive keys and
+// lane t of the block owns keys [t * KPL, (t + 1) * KPL) of it, a blocked
+// arrangement, read as KPL * sizeof(key) / 16 loads of 16 bytes when the run
+// is 16-byte aligned and the tile is whole (else key by key, guarded by n).
+// A lane compares its keys in registers; the one neighbour across a lane
+// boundary, the last key of the lane below, arrives by __shfl_up; lane 0 of a
+// wave has no lane below and loads the key before its first from global
+// memory, the one second load across a wave or tile boundary.  The heads of
+// a lane are a KPL-bit mask.
+//   uniq_count_k   block b walks its contiguous range of tiles; per key slot j
+//                  one ballot of "slot j is a head", and the popcounts add up
+//                  to the wave's heads.  One int64 per block.
+//   uniq_scan_k    one block: the exclusive scan of the per-block counts and
+//                  the total U, which the host reads back (the one stream
+//                  synchronisation) to size the outputs.
+//   uniq_write_k   the same walk re-flags the heads.  The heads held by the
+//                  lanes below come from the same ballots (popcount under the
+//                  lane mask), the waves below from a 4-entry LDS scan, the
+//                  tiles before from a running count and the blocks before
+//                  from the scan.  A head at run position i with slot u writes
+//                  key[i] (raw), pos[i] as first[u] and i as start[u], each
+//                  only when that output was asked for.
+//   uniq_edge_k /  counts[u] = start[u+1] - start[u] IN PLACE, with n closing
+//   uniq_diff_k    the last run: blocks own contiguous ranges of slots;
+//                  uniq_edge_k first saves every range's successor start (or
+//                  n), a launch boundary later uniq_diff_k walks each range
+//                  front to back, reading a chunk and its successor before a
+//                  barrier and writing after it.
+// No kernel waits for another block and there is no atomic: every output is
+// fixed by the input.
+// ---------------------------------------------------------------------------
+
+namespace {
+
+enum {
+    UNIQ_BLOCK = 256,
+    UNIQ_KPL = 16,                          // keys per lane
+    UNIQ_TILE = UNIQ_BLOCK * UNIQ_KPL,
+    UNIQ_GRID_CAP = 2048                    // 256 CUs x 8 blocks
+};
+
+struct UniqPlan {
+    int64_t ntiles, tpb;
+    int nblocks;
+};
+
+UniqPlan uniq_plan(int64_t n) {
+    UniqPlan p;
+    p.ntiles = (n + UNIQ_TILE - 1) / UNIQ_TILE;
+    p.tpb = (p.ntiles + UNIQ_GRID_CAP - 1) / UNIQ_GRID_CAP;
+    if (p.tpb < 1) p.tpb = 1;
+    p.nblocks = (int)((p.ntiles + p.tpb - 1) / p.tpb);
+    return p;
+}
+
+// int64 slots of the scratch: counts[nblocks], base[nblocks + 1] (the last is
+// U), edge[UNIQ_GRID_CAP]
+int64_t uniq_scratch_bytes(int64_t n) {
+    const UniqPlan p = uniq_plan(n);
+    return (((int64_t)2 * p.nblocks + 1 + UNIQ_GRID_CAP) * 8 + 15) & ~15LL;
+}
+
+template <typename U>
+__device__ __forceinline__ U uniq_shfl_up1(U v) {
+    if constexpr (sizeof(U) == 8)
+        return (U)__shfl_up((unsigned long long)v, 1);
+    else
+        return (U)__shfl_up((unsigned)v, 1);
+}
+
+// The lane's KPL raw keys of the tile at `base` (0 past n) and the mask of
+// its heads.  VEC: the run is 16-byte aligned.  Every lane of the block must
+// call (the shuffle), whatever it holds.
+template <typename T, bool VEC>
+__device__ __forceinline__ uint32_t uniq_heads(
+    const SortU<T> *__restrict__ keys, int64_t n, int64_t base, int t,
+    SortU<T> *raw) {
+    using U = SortU<T>;
+    const int64_t i0 = base + (int64_t)t * UNIQ_KPL;
+    if (VEC && base + UNIQ_TILE <= n) {
+        constexpr int NL = UNIQ_KPL * (int)sizeof(U) / 16;
+        const uint4 *src = reinterpret_cast<const uint4 *>(keys + i0);
+        uint4 q[NL];
+#pragma unroll
+        for (int k = 0; k < NL; ++k) q[k] = src[k];
+        __builtin_memcpy(raw, q, sizeof(q));
+    } else {
+#pragma unroll
+        for (int j = 0; j < UNIQ_KPL; ++j)
+            raw[j] = i0 + j < n ? keys[i0 + j] : (U)0;
+    }
+    U c[UNIQ_KPL];
+#pragma unroll
+    for (int j = 0; j < UNIQ_KPL; ++j) c[j] = rt_sort_canon<T>(raw[j]);
+    U prev = uniq_shfl_up1<U>(c[UNIQ_KPL - 1]);
+    bool first = false;                 // no key before this lane's first
+    if ((t & 63) == 0) {
+        if (i0 > 0 && i0 < n)
+            prev = rt_sort_canon<T>(keys[i0 - 1]);
+        else
+            first = true;
+    }
+    uint32_t heads = (i0 < n && (first || c[0] != prev)) ? 1u : 0u;
+#pragma unroll
+    for (int j = 1; j < UNIQ_KPL; ++j)
+        heads |= (i0 + j < n && c[j] != c[j - 1]) ? (1u << j) : 0u;
+    return heads;
+}
+
+template <typename T, bool VEC>
+__global__ __launch_bounds__(256) void uniq_count_k(
+    const SortU<T> *__restrict__ keys, int64_t n, int64_t tpb, int64_t ntiles,
+    int64_t *__restrict__ counts) {
+    __shared__ int64_t wsum[4];
+    const int t = threadIdx.x;
+    const int64_t tile0 = (int64_t)blockIdx.x * tpb;
+    const int64_t tile1 = tile0 + tpb < ntiles ? tile0 + tpb : ntiles;
+    int64_t mine = 0;                   // the wave's heads, the same in its lanes
+    for (int64_t tile = tile0; tile < tile1; ++tile) {
+        SortU<T> raw[UNIQ_KPL];
+        const uint32_t heads =
+            uniq_heads<T, VEC>(keys, n, tile * UNIQ_TILE, t, raw);
+#pragma unroll
+        for (int j = 0; j < UNIQ_KPL; ++j)
+            mine += __popcll(__ballot((heads >> j) & 1u));
+    }
+    if ((t & 63) == 0) wsum[t >> 6] = mine;
+    __syncthreads();
+    if (t == 0) counts[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+// one block: base[b] = counts[0] + .. + counts[b-1], base[nblocks] = U
+__global__ __launch_bounds__(256) void uniq_scan_k(
+    const int64_t *__restrict__ counts, int64_t *__restrict__ base,
+    int nblocks) {
+    __shared__ unsigned long long wsum[4];
+    const int t = threadIdx.x, w = t >> 6, lane = t & 63;
+    const int per = (nblocks + 255) / 256;
+    const int lo = t * per < nblocks ? t * per : nblocks;
+    const int hi = lo + per < nblocks ? lo + per : nblocks;
+    unsigned long long s = 0;
+    for (int i = lo; i < hi; ++i) s += (unsigned long long)counts[i];
+    const unsigned long long x = sort_wave_incl(s, lane);
+    if (lane == 63) wsum[w] = x;
+    __syncthreads();
+    unsigned long long run = x - s;
+    for (int k = 0; k < w; ++k) run += wsum[k];
+    for (int i = lo; i < hi; ++i) {
+        base[i] = (int64_t)run;
+        run += (unsigned long long)counts[i];
+    }
+    if (t == 255) base[nblocks] = (int64_t)run;
+}
+
+template <typename T, bool VEC>
+__global__ __launch_bounds__(256) void uniq_write_k(
+    const SortU<T> *__restrict__ keys, const int64_t *__restrict__ pos,
+    int64_t n, int64_t tpb, int64_t ntiles, const int64_t *__restrict__ base,
+    SortU<T> *__restrict__ out_keys, int64_t *__restrict__ out_first,
+    int64_t *__restrict__ out_start) {
+    __shared__ int wsum[2][4];          // double-buffered: one barrier a tile
+    const int t = threadIdx.x, w = t >> 6, lane = t & 63;
+    const unsigned long long lt_mask = (1ull << lane) - 1ull;
+    const int64_t tile0 = (int64_t)blockIdx.x * tpb;
+    const int64_t tile1 = tile0 + tpb < ntiles ? tile0 + tpb : ntiles;
+    int64_t run = base[blockIdx.x];     // slots used before this tile
+    int buf = 0;
+    for (int64_t tile = tile0; tile < tile1; ++tile, buf ^= 1) {
+        SortU<T> raw[UNIQ_KPL];
+        const int64_t tbase = tile * UNIQ_TILE;
+        const uint32_t heads = uniq_heads<T, VEC>(keys, n, tbase, t, raw);
+        int below = 0, wave = 0;        // heads in the lanes below; in the wave
+#pragma unroll
+        for (int j = 0; j < UNIQ_KPL; ++j) {
+            const unsigned long long b = __ballot((heads >> j) & 1u);
+            below += __popcll(b & lt_mask);
+            wave += __popcll(b);
+        }
+        if (lane == 0) wsum[buf][w] = wave;
+        __syncthreads();
+        int before = below, total = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int s = wsum[buf][k];
+            before += k < w ? s : 0;
+            total += s;
+        }
+        const int64_t i0 = tbase + (int64_t)t * UNIQ_KPL;
+#pragma unroll
+        for (int j = 0; j < UNIQ_KPL; ++j) {
+            if ((heads >> j) & 1u) {
+                const int64_t u =
+                    run + before + __popc(heads & ((1u << j) - 1u));
+                if (out_keys) out_keys[u] = raw[j];
+                if (out_first) out_first[u] = pos ? pos[i0 + j] : i0 + j;
+                if (out_start) out_start[u] = i0 + j;
+            }
+        }
+        run += total;
+    }
+}
+
+// The U starts are cut into at most UNIQ_GRID_CAP contiguous ranges of `per`
+// slots, a multiple of 256; U is read where uniq_scan_k left it, so the host
+// need not know it and the launch is UNIQ_GRID_CAP ranges wide, the ranges
+// past U empty.
+__device__ __forceinline__ int64_t uniq_range(int64_t nu) {
+    const int64_t per = (nu + UNIQ_GRID_CAP - 1) / UNIQ_GRID_CAP;
+    return (per + 255) / 256 * 256;
+}
+
+__global__ __launch_bounds__(256) void uniq_edge_k(
+    const int64_t *__restrict__ start, const int64_t *__restrict__ nu_p,
+    int64_t n, int64_t *__restrict__ edge) {
+    const int64_t nu = *nu_p, per = uniq_range(nu);
+    const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (b >= UNIQ_GRID_CAP) return;
+    const int64_t next = (b + 1) * per;
+    edge[b] = next < nu ? start[next] : n;
+}
+
+__global__ __launch_bounds__(256) void uniq_diff_k(
+    int64_t *__restrict__ start, const int64_t *__restrict__ nu_p,
+    const int64_t *__restrict__ edge) {
+    const int64_t nu = *nu_p, per = uniq_range(nu);
+    const int64_t lo = (int64_t)blockIdx.x * per;
+    const int64_t hi = lo + per < nu ? lo + per : nu;
+    const int64_t last = edge[blockIdx.x];
+    for (int64_t u0 = lo; u0 < hi; u0 += 256) {     // block-uniform bounds
+        const int64_t u = u0 + threadIdx.x;
+        int64_t a = 0, b = 0;
+        if (u < hi) {
+            a = start[u];
+            b = u + 1 < hi ? start[u + 1] : last;
+        }
+        __syncthreads();                // every read of this chunk is done
+        if (u < hi) start[u] = b - a;
+    }
+}
+
+template <typename T>
+int uniq_count_run(hipStream_t st, const void *keys, int64_t n, void *scratch,
+                   int64_t *n_unique) {
+    using U = SortU<T>;
+    const UniqPlan p = uniq_plan(n);
+    int64_t *counts = static_cast<int64_t *>(scratch);
+    int64_t *base = counts + p.nblocks;
+    const U *k = static_cast<const U *>(keys);
+    if (reinterpret_cast<uintptr_t>(keys) % 16 == 0)
+        uniq_count_k<T, true><<<p.nblocks, 256, 0, st>>>(k, n, p.tpb, p.ntiles,
+                                                         counts);
+    else
+        uniq_count_k<T, false><<<p.nblocks, 256, 0, st>>>(k, n, p.tpb,
+                                                          p.ntiles, counts);
+    uniq_scan_k<<<1, 256, 0, st>>>(counts, base, p.nblocks);
+    if (launched("rt_unique_count")) return 1;
+    int64_t total = 0;
+    HIP_CHECK(hipMemcpyAsync(&total, base + p.nblocks, sizeof(total),
+                             hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    *n_unique = total;
+    return 0;
+}
+
+template <typename T>
+int uniq_write_run(hipStream_t st, const void *keys, const void *pos,
+                   int64_t n, void *scratch, void *out_keys, void *out_first,
+                   void *out_counts) {
+    using U = SortU<T>;
+    const UniqPlan p = uniq_plan(n);
+    int64_t *base = static_cast<int64_t *>(scratch) + p.nblocks;
+    int64_t *edge = base + p.nblocks + 1;
+    const U *k = static_cast<const U *>(keys);
+    if (reinterpret_cast<uintptr_t>(keys) % 16 == 0)
+        uniq_write_k<T, true><<<p.nblocks, 256, 0, st>>>(
+            k, static_cast<const int64_t *>(pos), n, p.tpb, p.ntiles, base,
+            static_cast<U *>(out_keys), static_cast<int64_t *>(out_first),
+            static_cast<int64_t *>(out_counts));
+    else
+        uniq_write_k<T, false><<<p.nblocks, 256, 0, st>>>(
+            k, static_cast<const int64_t *>(pos), n, p.tpb, p.ntiles, base,
+            static_cast<U *>(out_keys), static_cast<int64_t *>(out_first),
+            static_cast<int64_t *>(out_counts));
+    if (launched("rt_unique_write")) return 1;
+    if (!out_counts) return 0;
+    uniq_edge_k<<<UNIQ_GRID_CAP / 256, 256, 0, st>>>(
+        static_cast<int64_t *>(out_counts), base + p.nblocks, n, edge);
+    uniq_diff_k<<<UNIQ_GRID_CAP, 256, 0, st>>>(
+        static_cast<int64_t *>(out_counts), base + p.nblocks, edge);
+    return launched("rt_unique_write counts");
+}
+
+}  // namespace
+
+extern "C" int rt_unique_geometry(int *block, int *keys_per_lane,
+                                  int *grid_cap) {
+    if (block) *block = UNIQ_BLOCK;
+    if (keys_per_lane) *keys_per_lane = UNIQ_KPL;
+    if (grid_cap) *grid_cap = UNIQ_GRID_CAP;
+    return 0;
+}
+
+extern "C" int64_t rt_unique_scratch(int64_t n) {
+    if (n < 0 || n >= (1LL << 40)) return -1;
+    return uniq_scratch_bytes(n);
+}
+
+namespace {
+
+int uniq_validate(const char *who, const void *keys, int64_t n, int dtype,
+                  const void *scratch) {
+    if (dtype < RT_F64 || dtype > RT_U8) return fail(who, "bad dtype");
+    if (n < 0) return fail(who, "negative n");
+    if (n >= (1LL << 40)) return fail(who, "n out of range");
+    if (n == 0) return 0;
+    if (!keys) return fail(who, "NULL keys");
+    if (!scratch) return fail(who, "NULL scratch");
+    if (reinterpret_cast<uintptr_t>(scratch) & 15)
+        return fail(who, "scratch not 16-byte aligned");
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int rt_unique_count(uintptr_t stream, const void *keys, int64_t n,
+                               int dtype, void *scratch,
+                               int64_t scratch_bytes, int64_t *n_unique) {
+    const char *who = "rt_unique_count";
+    if (uniq_validate(who, keys, n, dtype, scratch)) return 1;
+    if (!n_unique) return fail(who, "NULL n_unique");
+    *n_unique = 0;
+    if (n == 0) return 0;
+    if (scratch_bytes < uniq_scratch_bytes(n))
+        return fail(who, "scratch_bytes too small (rt_unique_scratch)");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    return dtype_dispatch<7>(who, dtype, [&](auto t) {
+        return uniq_count_run<decltype(t)>(st, keys, n, scratch, n_unique);
+    });
+}
+
+extern "C" int rt_unique_write(uintptr_t stream, const void *keys,
+                               const void *pos, int64_t n, int dtype,
+                               void *scratch, void *out_keys, void *out_first,
+                               void *out_counts) {
+    const char *who = "rt_unique_write";
+    if (uniq_validate(who, keys, n, dtype, scratch)) return 1;
+    if (n == 0) return 0;
+    if (!out_keys && !out_first && !out_counts)
+        return fail(who, "NULL out_keys, out_first and out_counts");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    return dtype_dispatch<7>(who, dtype, [&](auto t) {
+        return uniq_write_run<decltype(t)>(st, keys, pos, n, scratch, out_keys,
+                                           out_first, out_counts);
+    });
+}
+
+// ---------------------------------------------------------------------------
+// searchsorted (numpy.searchsorted; the reference has none): for every
+// needle of a strided box, how many of the m sorted keys sort strictly before
+// it (side 0, left) or not after it (side 1, right), in the canonical order.
+// rt_sort_bounds is the W-1 splitter form, one thread a splitter and every
+// probe in HBM; this is the kernel for 10^8 needles.
+//
+// The search, search_count: a lower / upper bound over cnt keys in a FIXED
+// number of trips with no branch: `lo` and the remaining length `len` start
+// at 0 and cnt; a trip probes key[lo + half - 1], half = len / 2, adds half
+// to lo when the probe is on the needle's low side and takes half off len.
+// The answer stays in [lo, lo + len]; len reaches 1 after ceil(log2 cnt)
+// trips and further trips do nothing (half = 0, the probe is clamped to
+// key[lo]), so the host fixes the trip count from the size alone and a wave
+// never diverges.  One last probe of key[lo] closes it.
+//
+// LDS regime, m <= SRCH_LDS_BYTES / key width: every block stages all of v,
+// as canonical keys, in 64 KB of LDS (two blocks fit the CU's 160 KB) and
+// then grid-strides over the needles; no probe leaves the CU.
+// FENCE regime, larger m: with seg = ceil(m / SRCH_FENCE) the block stages
+// the G = ceil(m / seg) <= SRCH_FENCE keys v[0], v[seg], v[2 seg], ..; only
+// real keys, no padding, so no needle value needs a special case.  A needle
+// takes j = search_count(fence) in LDS.  j == 0: v[0] is already on the high
+// side, the answer is 0.  Else fence[j-1] = v[(j-1) seg] is on the low side
+// and v[j seg], if it exists, is not, so the answer lies in ((j-1) seg,
+// j seg] and is (j-1) seg + search_count(v[(j-1) seg .. min(j seg, m))): one
+// segment of at most seg keys in global memory, trips fixed by seg.  This
+// holds for either side because "low side" is the same predicate in the
+// fence and in the segment, and it holds when a run of duplicates spans many
+// fence entries: the predicate is monotone over the sorted keys, the fence
+// is a subsequence of them, and the fence search returns the boundary of
+// the predicate in that subsequence, whichever entries are equal.
+//
+// Needles are walked as rt_hist walks its box (hist_box_args: 16-byte loads
+// under the rt_arg_flat rule, else by element) and the results are written
+// dense in C order.
+// ---------------------------------------------------------------------------
+
+namespace {
+
+enum {
+    SRCH_BLOCK = 256,
+    SRCH_FENCE = 4096,
+    SRCH_LDS_BYTES = 64 * 1024,
+    SRCH_GRID_CAP = 1024                    // 256 CUs x 2 blocks x 2
+};
+
+struct SearchArgs {
+    HistArgs box;            // the walk of the needles
+    int64_t m, seg;          // keys; FENCE: keys per segment, else 0
+    int lds_n;               // keys staged in LDS (m, or the fence's G)
+    int lds_trips, seg_trips, right;
+};
+
+int search_trips(int64_t cnt) {
+    int t = 0;
+    while (((int64_t)1 << t) < cnt) ++t;
+    return t;
+}
+
+// CANON: `key` holds canonical keys (LDS), else raw keys (global memory)
+template <typename T, bool CANON>
+__device__ __forceinline__ int64_t search_count(
+    const SortU<T> *key, int64_t cnt, int trips, SortU<T> x, int right) {
+    using U = SortU<T>;
+    if (cnt == 0) return 0;             // uniform: cnt is the same in a block
+    int64_t lo = 0, len = cnt;
+    for (int i = 0; i < trips; ++i) {
+        const int64_t half = len >> 1;
+        const U raw = key[lo + (half ? half - 1 : 0)];
+        const U k = CANON ? raw : rt_sort_canon<T>(raw);
+        const bool low = k < x || (right && k == x);
+        lo += low ? half : 0;
+        len -= half;
+    }
+    const U raw = key[lo];
+    const U k = CANON ? raw : rt_sort_canon<T>(raw);
+    return lo + ((k < x || (right && k == x)) ? 1 : 0);
+}
+
+template <typename T>
+__device__ __forceinline__ int64_t search_one(
+    const SearchArgs &s, const SortU<T> *lds, const SortU<T> *__restrict__ v,
+    SortU<T> needle) {
+    const SortU<T> x = rt_sort_canon<T>(needle);
+    const int64_t j =
+        search_count<T, true>(lds, s.lds_n, s.lds_trips, x, s.right);
+    if (s.seg == 0 || j == 0) return j;
+    const int64_t s0 = (j - 1) * s.seg;
+    const int64_t cnt = s.m - s0 < s.seg ? s.m - s0 : s.seg;
+    return s0 + search_count<T, false>(v + s0, cnt, s.seg_trips, x, s.right);
+}
+
+template <typename T, typename L>
+__global__ __launch_bounds__(256) void search_kernel(
+    const SortU<T> *__restrict__ v, const SortU<T> *__restrict__ in,
+    SearchArgs s, int64_t *__restrict__ out) {
+    using U = SortU<T>;
+    extern __shared__ __align__(16) unsigned char search_lds[];
+    U *lds = reinterpret_cast<U *>(search_lds);
+    const int tid = threadIdx.x;
+    const int64_t step = s.seg ? s.seg : 1;
+    for (int k = tid; k < s.lds_n; k += 256)
+        lds[k] = rt_sort_canon<T>(v[(int64_t)k * step]);
+    __syncthreads();
+
+    constexpr int PER = sizeof(L) / sizeof(U);
+    const HistArgs &a = s.box;
+    const L *src = reinterpret_cast<const L *>(in);
+    const int64_t S = (int64_t)gridDim.x * 256;
+    for (int64_t u = a.u0 + (int64_t)blockIdx.x * 256 + tid; u < a.u1; u += S) {
+        const L unit = src[hist_unit_off(a, u)];
+        U e[PER];
+        __builtin_memcpy(e, &unit, sizeof(L));
+#pragma unroll
+        for (int j = 0; j < PER; ++j)
+            out[u * PER + j] = search_one<T>(s, lds, v, e[j]);
+    }
+    const int64_t t = (int64_t)blockIdx.x * 256 + tid;
+    if (t < a.tailn)
+        out[a.tail0 + t] = search_one<T>(s, lds, v, in[a.tail0 + t]);
+}
+
+template <typename T, typename L>
+int search_launch(hipStream_t st, const void *v, const void *src,
+                  const SearchArgs &s, int64_t nunits, void *out) {
+    using U = SortU<T>;
+    int64_t blocks = (nunits + 255) / 256;
+    if (blocks > SRCH_GRID_CAP) blocks = SRCH_GRID_CAP;
+    if (blocks < 1) blocks = 1;             // the scalar tail alone
+    hipLaunchKernelGGL((search_kernel<T, L>), dim3((unsigned)blocks),
+                       dim3(256), (size_t)s.lds_n * sizeof(U), st,
+                       static_cast<const U *>(v), static_cast<const U *>(src),
+                       s, static_cast<int64_t *>(out));
+    return launched("rt_searchsorted");
+}
+
+}  // namespace
+
+extern "C" int rt_searchsorted_geometry(int *block, int *fence,
+                                        int64_t *lds_max, int *grid_cap) {
+    if (block) *block = SRCH_BLOCK;
+    if (fence) *fence = SRCH_FENCE;
+    if (lds_max)
+        for (int k = 0; k < 4; ++k) lds_max[k] = SRCH_LDS_BYTES >> k;
+    if (grid_cap) *grid_cap = SRCH_GRID_CAP;
+    return 0;
+}
+
+extern "C" int rt_searchsorted(uintptr_t stream, const void *v, int64_t m,
+                               const void *x, int64_t x_off, int nd,
+                               const int64_t *shape, const int64_t *strides,
+                               int dtype, int side, void *out) {
+    const char *who = "rt_searchsorted";
+    int64_t n;
+    if (box_extents(who, nd, 1, shape, strides, strides, &n)) return 1;
+    if (dtype < RT_F64 || dtype > RT_U8) return fail(who, "bad dtype");
+    if (side != 0 && side != 1) return fail(who, "bad side");
+    if (m < 0) return fail(who, "negative m");
+    if (m >= (1LL << 40)) return fail(who, "m out of range");
+    if (m > 0 && !v) return fail(who, "NULL v");
+    if (n == 0) return 0;
+    if (!x) return fail(who, "NULL x");
+    if (!out) return fail(who, "NULL out");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    return dtype_dispatch<7>(who, dtype, [&](auto t) {
+        using T = decltype(t);
+        SearchArgs s;
+        int64_t nunits;
+        const bool vec = hist_box_args(x, x_off, nd, shape, strides, sizeof(T),
+                                       n, &s.box, &nunits);
+        s.box.nbins = 0, s.box.regime = 0, s.box.stage_edges = 0;
+        s.box.u0 = 0, s.box.u1 = nunits;
+        s.m = m, s.right = side;
+        if (m <= SRCH_LDS_BYTES / (int64_t)sizeof(T)) {
+            s.seg = 0, s.seg_trips = 0;
+            s.lds_n = (int)m;
+        } else {
+            s.seg = (m + SRCH_FENCE - 1) / SRCH_FENCE;
+            s.seg_trips = search_trips(s.seg);
+            s.lds_n = (int)((m + s.seg - 1) / s.seg);
+        }
+        s.lds_trips = search_trips(s.lds_n);
+        const void *src = static_cast<const T *>(x) + x_off;
+        return vec ? search_launch<T, uint4>(st, v, src, s, nunits, out)
+                   : search_launch<T, SortU<T>>(st, v, src, s, nunits, out);
+    });
+}

@@ -110,6 +110,16 @@ _RT_ABI = {
                               _int, _int, ctypes.POINTER(ctypes.c_uint64),
                               _vp, _vp, _vp, _i64, _vp]),
     "rt_select_geometry": (_int, [ctypes.POINTER(_int)] * 4),
+    "rt_unique_count": (_int, [_sz, _vp, _i64, _int, _vp, _i64, _p64]),
+    "rt_unique_write": (_int, [_sz, _vp, _vp, _i64, _int, _vp, _vp, _vp,
+                               _vp]),
+    "rt_unique_scratch": (_i64, [_i64]),
+    "rt_unique_geometry": (_int, [ctypes.POINTER(_int)] * 3),
+    "rt_searchsorted": (_int, [_sz, _vp, _i64, _vp, _i64, _int, _p64, _p64,
+                               _int, _int, _vp]),
+    "rt_searchsorted_geometry": (_int, [ctypes.POINTER(_int),
+                                        ctypes.POINTER(_int), _p64,
+                                        ctypes.POINTER(_int)]),
     "rt_stream_sync": (_int, [_sz]),
     "rt_device_sync": (_int, []),
     "rt_event_create": (_int, [_pvp]),
@@ -174,6 +184,27 @@ def select_geometry(lib):
     lib.rt_select_geometry(*[ctypes.byref(v) for v in vals])
     return dict(zip(("grid_cap", "block", "nq_max", "digit_bits"),
                     (v.value for v in vals)))
+
+
+def unique_geometry(lib):
+    """rt_unique_geometry as a dict (host arithmetic; needs no GPU).  `tile`
+    is block x keys_per_lane."""
+    blk, kpl, cap = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    lib.rt_unique_geometry(ctypes.byref(blk), ctypes.byref(kpl),
+                           ctypes.byref(cap))
+    return {"block": blk.value, "keys_per_lane": kpl.value,
+            "tile": blk.value * kpl.value, "grid_cap": cap.value}
+
+
+def searchsorted_geometry(lib):
+    """rt_searchsorted_geometry as a dict (host arithmetic; needs no GPU);
+    `lds_max` is by key width in bytes."""
+    blk, fence, cap = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    lmax = (ctypes.c_int64 * 4)()
+    lib.rt_searchsorted_geometry(ctypes.byref(blk), ctypes.byref(fence), lmax,
+                                 ctypes.byref(cap))
+    return {"block": blk.value, "fence": fence.value, "grid_cap": cap.value,
+            "lds_max": {1 << k: int(lmax[k]) for k in range(4)}}
 
 
 def _hb_arg_chunks(nd, axis, nout, K):
@@ -1389,6 +1420,73 @@ class HipBackend:
             ctypes.c_void_p(spl.data_ptr()), m,
             ctypes.c_void_p(out.data_ptr())), "rt_sort_bounds")
         return out.cpu().numpy()
+
+    # -- unique / searchsorted (runtime.unique_op, searchsorted_op) -----------
+    #
+    # The hooks of ramba_amd/setops.py on the rt_unique_* and rt_searchsorted
+    # kernels.  Runs and results are dense tensors; needles are read in place
+    # in the container.
+
+    setops_dtypes = frozenset(RT_DTYPE)     # the ops refuse any other, by name
+
+    def unique_run(self, keys, pos, want_first, want_counts):
+        torch = self.torch
+        n = int(keys.numel())
+        i64 = torch.int64
+        if n == 0:
+            return (keys[:0], torch.empty(0, dtype=i64, device="cuda")
+                    if want_first else None,
+                    torch.empty(0, dtype=i64, device="cuda")
+                    if want_counts else None)
+        keys = keys.contiguous()
+        dtc = RT_DTYPE[str(keys.dtype).replace("torch.", "")]
+        nbytes = int(self.lib.rt_unique_scratch(n))
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+        nu = ctypes.c_int64()
+        self._check(self.lib.rt_unique_count(
+            self._stream(), ctypes.c_void_p(keys.data_ptr()), n, dtc,
+            ctypes.c_void_p(scratch.data_ptr()), nbytes, ctypes.byref(nu)),
+            "rt_unique_count")
+        ukeys = torch.empty(nu.value, dtype=keys.dtype, device="cuda")
+        first = torch.empty(nu.value, dtype=i64, device="cuda") \
+            if want_first else None
+        counts = torch.empty(nu.value, dtype=i64, device="cuda") \
+            if want_counts else None
+        if pos is not None:
+            pos = pos.contiguous()
+        self._check(self.lib.rt_unique_write(
+            self._stream(), ctypes.c_void_p(keys.data_ptr()),
+            ctypes.c_void_p(pos.data_ptr()) if pos is not None else None,
+            n, dtc, ctypes.c_void_p(scratch.data_ptr()),
+            ctypes.c_void_p(ukeys.data_ptr()),
+            ctypes.c_void_p(first.data_ptr()) if want_first else None,
+            ctypes.c_void_p(counts.data_ptr()) if want_counts else None),
+            "rt_unique_write")
+        return ukeys, first, counts
+
+    def search_core(self, v, bd, rt, out_bd, side):
+        d, _, cstr, pads = rt.shard_geometry(bd)
+        if d is None:
+            return
+        shape = tuple(int(x) for x in box_shape(d))
+        nd = len(shape)
+        off = sum(pads[i] * cstr[i] for i in range(nd))
+        v = v.contiguous()
+        _, _, _, opads = rt.shard_geometry(out_bd)
+        core = self._cont(out_bd)[tuple(
+            slice(opads[i], opads[i] + shape[i]) for i in range(nd))]
+        # a 1-D core is dense in its container: the kernel writes it in place
+        res = core if core.is_contiguous() else self.torch.empty(
+            shape, dtype=self.torch.int64, device="cuda")
+        self._check(self.lib.rt_searchsorted(
+            self._stream(),
+            ctypes.c_void_p(v.data_ptr()) if v.numel() else None,
+            int(v.numel()), ctypes.c_void_p(self._cont(bd).data_ptr()),
+            int(off), nd, _i64arr(shape), _i64arr(cstr),
+            RT_DTYPE[str(np.dtype(bd.dtype))], int(side == "right"),
+            ctypes.c_void_p(res.data_ptr())), "rt_searchsorted")
+        if res is not core:
+            core.copy_(res)
 
     # -- cross-stage fusion (staged/tiled kernel; ramba_amd/staged.py) --------
 

@@ -1576,6 +1576,110 @@ ndarray._ARRAY_FUNC.update({
 })
 
 
+# -- unique / searchsorted on runtime.unique_op / searchsorted_op.  unique
+#    ravels the array onto contiguous divisions through the engine (as sort
+#    with axis=None does), sorts it and compacts the runs; the inverse is a
+#    searchsorted of the array in its own distinct values.  Sync points, like
+#    take and sort. -----------------------------------------------------------
+
+def _from_bd(bd):
+    return ndarray(bd, View.identity(bd.shape))
+
+
+def unique(ar, return_index=False, return_inverse=False, return_counts=False,
+           axis=None, *, equal_nan=True):
+    """numpy.unique for ramba arrays: the sorted distinct values and, on
+    request, the int64 first indices, inverse (of ar's shape) and counts, as
+    ramba arrays.  -0.0 equals +0.0 and all NaNs are one value; the value
+    kept is the first occurrence.  axis=, equal_nan=False on floats, complex
+    input and more than 4 axes are not supported."""
+    if not isinstance(ar, ndarray):
+        return np.unique(ar, return_index=return_index,
+                         return_inverse=return_inverse,
+                         return_counts=return_counts, axis=axis,
+                         equal_nan=equal_nan)
+    if axis is not None:
+        raise NotImplementedError(
+            "unique: axis= is not supported (only the flattened array is "
+            "compacted; rows are not compared)")
+    if ar.dtype.kind == "c":
+        raise NotImplementedError("unique: complex input is not supported")
+    if not equal_nan and ar.dtype.kind == "f":
+        raise NotImplementedError(
+            "unique: equal_nan=False is not supported on float input (every "
+            "NaN is one value in the sort order)")
+    if ar.ndim > 4:
+        raise NotImplementedError(
+            "unique supports arrays of up to 4 dimensions")
+    if ar.size == 0:
+        out = [zeros(0, dtype=ar.dtype)]
+        out += [zeros(0, dtype=np.int64)] if return_index else []
+        out += [zeros(ar.shape, dtype=np.int64)] if return_inverse else []
+        out += [zeros(0, dtype=np.int64)] if return_counts else []
+        return out[0] if len(out) == 1 else tuple(out)
+    rt = deferred.get_runtime()
+    src = _gemm_operand(ar if ar.ndim == 1 else ar.ravel(), ar.dtype, rt)
+    deferred.flush()
+    vals_bd, idx_bd, cnt_bd = rt.unique_op(src, bool(return_index),
+                                           bool(return_counts))
+    out = [_from_bd(vals_bd)]
+    if return_index:
+        out.append(_from_bd(idx_bd))
+    if return_inverse:
+        out.append(searchsorted(out[0], ar, side="left"))
+    if return_counts:
+        out.append(_from_bd(cnt_bd))
+    return out[0] if len(out) == 1 else tuple(out)
+
+
+def searchsorted(a, v, side="left", sorter=None):
+    """numpy.searchsorted when `a` or `v` is a ramba array: `a` is 1-D and
+    sorted (not checked, as in NumPy), `v` a scalar (the result is a host
+    np.int64) or an array of up to 4 axes (a ramba int64 array of its
+    shape).  Both are cast to np.result_type of the two; `a` is replicated
+    on every rank, so it must fit on one GPU.  sorter= is not supported."""
+    if not isinstance(a, ndarray) and not isinstance(v, ndarray):
+        return np.searchsorted(a, v, side=side, sorter=sorter)
+    if sorter is not None:
+        raise NotImplementedError(
+            "searchsorted: sorter= is not supported; sort the array first")
+    if side not in ("left", "right"):
+        raise ValueError(
+            f"search side must be 'left' or 'right' (got '{side}')")
+    if not isinstance(a, ndarray):
+        a = np.asarray(a)
+    if not isinstance(v, ndarray):
+        v = np.asarray(v)
+    if a.ndim != 1:         # NumPy's own error for this depth
+        np.searchsorted(np.empty((0,) * a.ndim), 0)
+    dt = np.result_type(a.dtype, v.dtype)
+    if str(dt) not in ("float64", "float32", "int64", "int32", "int16",
+                       "int8", "uint8", "bool"):
+        raise NotImplementedError(
+            f"searchsorted: no search kernel for dtype {dt}")
+    if v.ndim > 4:
+        raise NotImplementedError(
+            "searchsorted supports needle arrays of up to 4 dimensions")
+    scalar = v.ndim == 0
+    if a.size == 0 or v.size == 0:
+        return np.int64(0) if scalar else zeros(v.shape, dtype=np.int64)
+    if not isinstance(a, ndarray):
+        a = fromarray(a.astype(dt))
+    if not isinstance(v, ndarray):
+        v = fromarray(v.astype(dt).reshape(1) if scalar else v.astype(dt))
+    rt = deferred.get_runtime()
+    deferred.flush()
+    a, v = _gemm_operand(a, dt, rt), _gemm_operand(v, dt, rt)
+    deferred.flush()
+    res = _from_bd(rt.searchsorted_op(a, v, side))
+    return np.int64(res.asarray()[0]) if scalar else res
+
+
+ndarray.searchsorted = lambda self, v, side="left", sorter=None: \
+    searchsorted(self, v, side=side, sorter=sorter)
+ndarray._ARRAY_FUNC.update({"unique": unique, "searchsorted": searchsorted})
+
+
 # -- median / percentile / quantile and their nan variants.  axis=None runs
 #    on runtime.select_op, a radix select that moves no data: the wanted
 #    ranks go in, canonical keys come back and are decoded on the host, and

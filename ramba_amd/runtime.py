@@ -1522,6 +1522,29 @@ def sort_op(self, arr, axis, want_index):
         hooks.sort_lines(bd, self, out_bd, want_index)
         return out_bd
 
+    skeys, sidx, total = _sorted_run(self, bd, hooks, not want_index,
+                                     want_index)
+    out_bd = self.new_result(bd.shape, out_dtype, _run_divisions(total))
+    if total[self.rank]:
+        self.backend.write_local_dense(out_bd, self,
+                                       sidx if want_index else skeys)
+    self.backend.free_temps()
+    return out_bd
+
+
+def _run_divisions(total):
+    """1-D divisions whose rank r holds total[r] consecutive elements."""
+    ends = np.cumsum(total)
+    boxes = [None if total[r] == 0 else
+             np.array([[int(ends[r] - total[r])], [int(ends[r]) - 1]])
+             for r in range(len(total))]
+    return divisions_from_boxes(boxes, 1)
+
+
+def _sorted_run(self, bd, hooks, want_keys, want_index):
+    """The rank's segment of the globally sorted 1-D array `bd` after the
+    sample sort described above: (keys, global indices, per-rank segment
+    sizes); keys / indices not asked for are None."""
     W, me = self.world, self.rank
     core = self.core_box(bd, me)
     start = 0 if core is None else int(core[0, 0])
@@ -1568,23 +1591,111 @@ def sort_op(self, arr, axis, want_index):
 
     rkeys = swap(keys, bd.dtype)
     ridx = swap(gidx, np.dtype(np.int64)) if want_index else None
-    skeys, sidx = hooks.sort_run(rkeys, ridx, 0, not want_index, want_index)
+    skeys, sidx = hooks.sort_run(rkeys, ridx, 0, want_keys, want_index)
+    return skeys, sidx, counts.sum(axis=0)
 
-    total = counts.sum(axis=0)
-    ends = np.cumsum(total)
-    boxes = [None if total[r] == 0 else
-             np.array([[int(ends[r] - total[r])], [int(ends[r]) - 1]])
-             for r in range(W)]
-    out_bd = self.new_result(bd.shape, out_dtype,
-                             divisions_from_boxes(boxes, 1))
-    if total[me]:
-        self.backend.write_local_dense(out_bd, self,
-                                       sidx if want_index else skeys)
+
+Runtime.sort_op = sort_op
+
+
+# ---------------------------------------------------------------------------
+# unique / searchsorted (numpy.unique, numpy.searchsorted; the reference has
+# neither), through the hooks of ramba_amd/setops.py.
+#
+# unique_op: sort (with the global index as the payload when the first
+# occurrences are wanted), then compact the runs of the rank's sorted segment
+# (the rt_unique_* kernels), then allgather the per-rank number of distinct
+# values; the results' divisions follow those numbers, as those of a[mask]
+# and of the sample sort do.  No boundary exchange is needed: by the splitter
+# rule above sort_op, bucket j gets the keys k with s[j-1] <= k < s[j] in the
+# canonical order, so ALL keys equal to one value, a splitter or not, fall in
+# one bucket and reach one rank.  No run of equal keys straddles two ranks,
+# every rank's run heads are global run heads, and its counts are complete.
+# The payload sort is stable, so a head's payload is the value's first
+# occurrence.
+#
+# searchsorted_op: the sorted keys are gathered dense onto every rank, as
+# matvec_op replicates x; the needles stay where they are and the result has
+# their shape and divisions.  Limit: the keys must fit on one GPU.
+# ---------------------------------------------------------------------------
+
+def _setops_hooks(self, who, dtype):
+    from .setops import hooks_for
+    hooks = hooks_for(self.backend)
+    known = getattr(hooks, "setops_dtypes", None)   # None: any NumPy dtype
+    if known is not None and str(np.dtype(dtype)) not in known:
+        raise NotImplementedError(f"{who}: no kernel for dtype {dtype}")
+    return hooks
+
+
+def unique_op(self, arr, want_index, want_counts):
+    """(values, first indices or None, counts or None) of the constructed
+    1-D `arr`, each a bdarray of U elements on the same divisions."""
+    from .sorting import hooks_for as sort_hooks_for
+    bd = arr.bdarray
+    assert len(bd.shape) == 1 and bd.shape[0] > 0 and bd.constructed \
+        and arr.view.is_identity_for(bd.shape) and np.array_equal(
+            bd.divisions, contiguous_divisions(self.world, bd.shape)), \
+        "unique_op: the frontend ravels and repartitions first"
+    hooks = _setops_hooks(self, "unique", bd.dtype)
+    shooks = sort_hooks_for(self.backend)
+    if self.world == 1:     # the local sort is the global one
+        skeys, sidx = shooks.sort_run(shooks.local_run(bd, self), None, 0,
+                                      True, want_index)
+    else:
+        skeys, sidx, _ = _sorted_run(self, bd, shooks, True, want_index)
+    ukeys, first, counts = hooks.unique_run(skeys, sidx, want_index,
+                                            want_counts)
+    mine = int(ukeys.shape[0])
+    per_rank = np.array([int(c) for c in self.backend.allgather_scalars(
+        np.int64(mine), np.int64)], dtype=np.int64)
+    divs = _run_divisions(per_rank)
+    out = []
+    for local, dtype in ((ukeys, bd.dtype), (first, np.dtype(np.int64)),
+                         (counts, np.dtype(np.int64))):
+        if local is None:
+            out.append(None)
+            continue
+        out_bd = self.new_result((int(per_rank.sum()),), dtype, divs)
+        if mine:
+            self.backend.write_local_dense(out_bd, self, local)
+        out.append(out_bd)
+    self.backend.free_temps()
+    return tuple(out)
+
+
+def searchsorted_op(self, v_arr, x_arr, side):
+    """For every element of the constructed array `x_arr` its insertion
+    point (int64) in the sorted constructed 1-D array `v_arr` of the same
+    dtype; the result has x_arr's shape and divisions."""
+    from . import gemm as _gemm
+    v_bd, x_bd = v_arr.bdarray, x_arr.bdarray
+    assert len(v_bd.shape) == 1 and v_bd.dtype == x_bd.dtype
+    _on_contiguous(self, "searchsorted_op", v_bd)
+    assert x_bd.constructed and x_arr.view.is_identity_for(x_bd.shape)
+    hooks = _setops_hooks(self, "searchsorted", v_bd.dtype)
+    W, me, m = self.world, self.rank, int(v_bd.shape[0])
+    v = _gemm.hooks_for(self.backend).gemv_vector(v_bd, self) if m else \
+        self.backend.new_message_buffer((0,), v_bd.dtype)
+    if W > 1 and m:
+        mine, v = v, self.backend.new_message_buffer((m,), v_bd.dtype)
+        sends = [(r, mine) for r in range(W) if r != me and mine.shape[0]]
+        recvs = []
+        for r in range(W):
+            k0, k1 = _span(v_bd, r)
+            if r == me:
+                v[k0:max(k1, k0)] = mine
+            elif k1 > k0:
+                recvs.append((r, v[k0:k1]))
+        self.backend.exchange(sends, recvs)
+    out_bd = self.new_result(x_bd.shape, np.dtype(np.int64), x_bd.divisions)
+    hooks.search_core(v, x_bd, self, out_bd, side)
     self.backend.free_temps()
     return out_bd
 
 
-Runtime.sort_op = sort_op
+Runtime.unique_op = unique_op
+Runtime.searchsorted_op = searchsorted_op
 
 
 # ---------------------------------------------------------------------------
