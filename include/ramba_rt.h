@@ -35,6 +35,8 @@
  *                       counterpart)
  *   rt_searchsorted   — batched binary search behind an LDS fence
  *                       (searchsorted; no reference counterpart)
+ *   rt_partition      — stable multi-pivot split of a dense run (partition /
+ *                       argpartition; no reference counterpart)
  *   rt_stream_sync /
  *   rt_device_sync    — worker-side completion (sync, ramba.py:9843)
  *   rt_event_*        — hot-loop timing (add_time, ramba.py:945-1022)
@@ -89,8 +91,8 @@ int rt_launch(void *kernel, unsigned gx, unsigned gy, unsigned gz,
               size_t argsize);
 
 /* Argument contract shared by rt_copy_box, rt_combine_box, rt_cumsum,
- * rt_mask_compact, rt_axis_scan, rt_flat_copy, rt_hist and the rt_sort
- * family (the contract of
+ * rt_mask_compact, rt_axis_scan, rt_flat_copy, rt_hist, rt_partition and the
+ * rt_sort family (the contract of
  * rt_take_rows): every argument is checked on the host before any HIP call
  * and a bad one returns nonzero with rt_last_error() naming the entry point
  * and the argument.  Rejected: nd out of range; NULL shape / strides; a
@@ -596,6 +598,55 @@ int rt_searchsorted(uintptr_t stream, const void *v, int64_t m, const void *x,
                     const int64_t *strides, int dtype, int side, void *out);
 int rt_searchsorted_geometry(int *block, int *fence, int64_t *lds_max,
                              int *grid_cap);
+
+/* partition / argpartition — numpy.partition / numpy.argpartition (the
+ * reference has neither): one stable split of a dense run about keys that
+ * rt_select_pass found.  in: n raw keys of `dtype` (any rt_dtype).  pivots: a
+ * HOST array of npiv, 1 <= npiv <= npiv_max (8), distinct ascending canonical
+ * keys (ramba_sortkey.h), no bit set above the key width.  The bucket of a
+ * key k is
+ *     b(k) = 2 * (number of pivots < canon(k)) + (canon(k) equals a pivot),
+ * 2 npiv + 1 buckets.  The output is the buckets in ascending order, each in
+ * input order (a stable split); the raw bits are moved, so zero signs and NaN
+ * payloads arrive as they were.  out (raw keys) or vals_out (int64 payloads)
+ * may be NULL, not both; the payload of key i is vals_in[i], or val0 + i when
+ * vals_in is NULL (vals_in = NULL, val0 = 0 is argpartition), as in rt_sort.
+ * bucket_counts: HOST int64[2 npiv + 1], may be NULL; it receives the bucket
+ * sizes.  When it is given the call synchronises the stream once, otherwise
+ * not at all.
+ * Three launches, none of which waits for another block, no atomics: the
+ * output is the same from run to run.  (1) At most grid_cap blocks, each over
+ * a contiguous range of tiles of block x keys_per_lane keys; a lane owns
+ * keys_per_lane CONSECUTIVE keys, read with 16-byte loads when the run is
+ * 16-byte aligned and the tile whole (else by element), computes their
+ * buckets in registers (the pivots are kernel arguments) and counts them in
+ * packed 16-bit fields, one per bucket but the last, whose counts are what is
+ * left; one int64 per bucket and block goes to the scratch.  (2) One block
+ * scans buckets and blocks.  (3) The same walk recomputes the buckets; a key
+ * goes to its bucket's base for the block (advanced tile by tile) + the
+ * counts of the waves below (a 4-entry LDS table) + one shuffle scan of the
+ * packed words over the wave (every bucket's prefix at once) + the lane's
+ * earlier keys, with direct stores.  npiv == 1, the top-k case, packs "below"
+ * and "equal" into one 32-bit word and derives the third bucket; npiv <= 4
+ * takes two 64-bit words, npiv <= 8 four.
+ * `in` / vals_in are only read and must not overlap out, vals_out or the
+ * scratch.  scratch: device memory, 16-byte aligned, of at least
+ * rt_partition_scratch(n, npiv) bytes (two int64 per bucket and block, under
+ * 1 MB).
+ * Validated before any HIP call: dtype, n < 0 or >= 2^40, npiv, NULL /
+ * unsorted / duplicate pivots, a pivot with bits above the key width, NULL in
+ * / scratch with work to do, out and vals_out both NULL, a misaligned or too
+ * small scratch.  n == 0 returns 0 without launching (bucket_counts zeroed).
+ * rt_partition_scratch (-1 for a bad n or npiv) and rt_partition_geometry
+ * (the compiled-in constants; any pointer may be NULL) are host arithmetic
+ * only. */
+int rt_partition(uintptr_t stream, const void *in, void *out,
+                 const void *vals_in, int64_t val0, void *vals_out, int64_t n,
+                 int dtype, int npiv, const uint64_t *pivots, void *scratch,
+                 int64_t scratch_bytes, int64_t *bucket_counts);
+int64_t rt_partition_scratch(int64_t n, int npiv);
+int rt_partition_geometry(int *block, int *keys_per_lane, int *grid_cap,
+                          int *npiv_max);
 
 int rt_stream_sync(uintptr_t stream);
 int rt_device_sync(void);

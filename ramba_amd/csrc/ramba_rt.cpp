@@ -4944,3 +4944,417 @@ extern "C" int rt_searchsorted(uintptr_t stream, const void *v, int64_t m,
                    : search_launch<T, SortU<T>>(st, v, src, s, nunits, out);
     });
 }
+
+// ---------------------------------------------------------------------------
+// partition / argpartition (numpy.partition, numpy.argpartition; the reference
+// has neither): the data movement around keys that rt_select_pass found, one
+// stable split of a dense run about P <= PART_NPIV_MAX pivots, distinct
+// ascending canonical keys.  The bucket of a key k is
+//     b(k) = 2 * (number of pivots < canon(k)) + (canon(k) equals a pivot),
+// 2P + 1 buckets: below the first pivot, equal to it, between the first two,
+// ..  The output is the buckets in ascending order, each in input order; the
+// raw bits are moved.  Three launches, none of which waits for another block,
+// no atomics: the output is fixed by the input.
+//
+// Tiling (count and scatter alike): a tile is PART_BLOCK x PART_KPL consecutive
+// keys and lane t owns keys [t * KPL, (t + 1) * KPL) of it, read as KPL *
+// sizeof(key) / 16 loads of 16 bytes when the run is 16-byte aligned and the
+// tile whole (else key by key, guarded by n).  A block walks a contiguous
+// range of tiles.  The buckets of a lane's keys are computed in registers
+// (the pivots are kernel arguments, compared in the key's own width) and
+// COUNTED IN PACKED WORDS: a word W holds sizeof(W) / 2 fields of 16 bits, one
+// per bucket; a lane adds 1 << 16 f for a key of bucket f.  A tile has 4096
+// keys, so no field of a lane, wave or tile sum can carry into the next, and
+// ONE shuffle scan of a word over the wave is the per-bucket prefix of all
+// its fields at once.  The last bucket, 2P, has no field: its counts are what
+// is left of the keys.  Word classes: P = 1, the top-k case: one uint32, the
+// two fields "below" and "equal", the third bucket derived; P <= 4: two
+// uint64; P <= 8: four uint64.
+//   part_count_k    per tile the wave's packed totals (the scan's last lane);
+//                   lane f of each wave keeps the running 64-bit count of
+//                   bucket f.  counts[bucket][block], int64.
+//   part_scan_k     one block: base[b][blk] = the keys of lower buckets + the
+//                   keys of bucket b in the blocks before; totals[b].
+//   part_scatter_k  the same walk recomputes the buckets.  A key of bucket f
+//                   goes to: the block's base of f (LDS, advanced tile by
+//                   tile) + field f of (the packed totals of the waves below,
+//                   a 4-entry LDS table, + the exclusive wave scan + the
+//                   lane's earlier keys).  Both LDS tables are double
+//                   buffered: one barrier a tile.  Stores are direct, key by
+//                   key: a lane's keys of one bucket are consecutive in the
+//                   output, and so are those of neighbouring lanes.
+// ---------------------------------------------------------------------------
+
+namespace {
+
+enum {
+    PART_BLOCK = 256,
+    PART_KPL = 16,                          // keys per lane
+    PART_TILE = PART_BLOCK * PART_KPL,      // < 2^16: a field holds a tile
+    PART_GRID_CAP = 2048,                   // 256 CUs x 8 blocks
+    PART_NPIV_MAX = 8,                      // = SELECT_NQ_MAX
+    PART_NB_MAX = 2 * PART_NPIV_MAX + 1
+};
+
+struct PartPivots {
+    uint64_t p[PART_NPIV_MAX];
+};
+
+struct PartPlan {
+    int64_t ntiles, tpb;
+    int nblocks;
+};
+
+PartPlan part_plan(int64_t n) {
+    PartPlan p;
+    p.ntiles = (n + PART_TILE - 1) / PART_TILE;
+    p.tpb = (p.ntiles + PART_GRID_CAP - 1) / PART_GRID_CAP;
+    if (p.tpb < 1) p.tpb = 1;
+    p.nblocks = (int)((p.ntiles + p.tpb - 1) / p.tpb);
+    return p;
+}
+
+// int64 slots of the scratch: counts[nb][nblocks], base[nb][nblocks],
+// totals[nb], nb = 2 npiv + 1
+int64_t part_scratch_bytes(int64_t n, int npiv) {
+    const PartPlan p = part_plan(n);
+    const int64_t nb = 2 * npiv + 1;
+    return ((2 * nb * p.nblocks + nb) * 8 + 15) & ~15LL;
+}
+
+template <typename W>
+__device__ __forceinline__ W part_shfl_up(W v, int off) {
+    if constexpr (sizeof(W) == 8)
+        return (W)__shfl_up((unsigned long long)v, off);
+    else
+        return (W)__shfl_up((unsigned)v, off);
+}
+
+template <typename W>
+__device__ __forceinline__ W part_wave_incl(W x, int lane) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const W y = part_shfl_up<W>(x, off);
+        if (lane >= off) x += y;
+    }
+    return x;
+}
+
+template <typename W>
+__device__ __forceinline__ W part_wave_last(W x) {
+    if constexpr (sizeof(W) == 8)
+        return (W)__shfl((unsigned long long)x, 63);
+    else
+        return (W)__shfl((unsigned)x, 63);
+}
+
+// one key of bucket f into the packed words; bucket nf (the last) has no field
+template <typename W, int NW>
+__device__ __forceinline__ void part_add(W *a, int f, int nf) {
+    constexpr int FPW = (int)sizeof(W) / 2;
+#pragma unroll
+    for (int k = 0; k < NW; ++k)
+        a[k] += (f < nf && f / FPW == k) ? (W)((W)1 << (16 * (f % FPW)))
+                                         : (W)0;
+}
+
+// field f < NW * FPW of the packed words
+template <typename W, int NW>
+__device__ __forceinline__ int part_field(const W *a, int f) {
+    constexpr int FPW = (int)sizeof(W) / 2;
+    W v = a[0];
+#pragma unroll
+    for (int k = 1; k < NW; ++k) v = f / FPW == k ? a[k] : v;
+    return (int)((v >> (16 * (f % FPW))) & (W)0xffff);
+}
+
+// the sum of every field (at most a tile: no carry)
+template <typename W, int NW>
+__device__ __forceinline__ int part_field_sum(const W *a) {
+    unsigned long long s = 0;
+#pragma unroll
+    for (int k = 0; k < NW; ++k) s += a[k];
+    s += s >> 32;
+    s += s >> 16;
+    return (int)(s & 0xffffull);
+}
+
+// The lane's KPL raw keys of the tile at `base` (0 past n), their buckets,
+// and the packed counts of the lane's valid keys.
+template <typename T, typename W, int NW, int PMAX>
+__device__ __forceinline__ void part_tile(
+    const SortU<T> *__restrict__ keys, int64_t n, int64_t base, int t,
+    bool vec, const PartPivots &pv, int npiv, SortU<T> *raw, uint8_t *bk,
+    W *w) {
+    using U = SortU<T>;
+    const int64_t i0 = base + (int64_t)t * PART_KPL;
+    if (vec && base + PART_TILE <= n) {
+        constexpr int NL = PART_KPL * (int)sizeof(U) / 16;
+        const uint4 *src = reinterpret_cast<const uint4 *>(keys + i0);
+        uint4 q[NL];
+#pragma unroll
+        for (int k = 0; k < NL; ++k) q[k] = src[k];
+        __builtin_memcpy(raw, q, sizeof(q));
+    } else {
+#pragma unroll
+        for (int j = 0; j < PART_KPL; ++j)
+            raw[j] = i0 + j < n ? keys[i0 + j] : (U)0;
+    }
+#pragma unroll
+    for (int k = 0; k < NW; ++k) w[k] = 0;
+#pragma unroll
+    for (int j = 0; j < PART_KPL; ++j) {
+        const U c = rt_sort_canon<T>(raw[j]);
+        int lt = 0, eq = 0;
+#pragma unroll
+        for (int q = 0; q < PMAX; ++q) {
+            const U p = (U)pv.p[q];
+            lt += (q < npiv && p < c) ? 1 : 0;
+            eq |= (q < npiv && p == c) ? 1 : 0;
+        }
+        bk[j] = (uint8_t)(2 * lt + eq);
+        if (i0 + j < n) part_add<W, NW>(w, bk[j], 2 * npiv);
+    }
+}
+
+template <typename T, typename W, int NW, int PMAX>
+__global__ __launch_bounds__(256) void part_count_k(
+    const SortU<T> *__restrict__ keys, int64_t n, int64_t tpb, int64_t ntiles,
+    int vec, PartPivots pv, int npiv, int64_t *__restrict__ counts) {
+    constexpr int FPW = (int)sizeof(W) / 2;
+    __shared__ int64_t wsum[4][2 * PART_NPIV_MAX];
+    const int t = threadIdx.x, wv = t >> 6, lane = t & 63;
+    const int nf = 2 * npiv;
+    const int64_t tile0 = (int64_t)blockIdx.x * tpb;
+    const int64_t tile1 = tile0 + tpb < ntiles ? tile0 + tpb : ntiles;
+    int64_t mine = 0;       // lane f < nf: the wave's keys of bucket f
+    for (int64_t tile = tile0; tile < tile1; ++tile) {
+        SortU<T> raw[PART_KPL];
+        uint8_t bk[PART_KPL];
+        W w[NW];
+        part_tile<T, W, NW, PMAX>(keys, n, tile * PART_TILE, t, vec != 0, pv,
+                                  npiv, raw, bk, w);
+#pragma unroll
+        for (int k = 0; k < NW; ++k) {
+            const W tot = part_wave_last<W>(part_wave_incl<W>(w[k], lane));
+            if (lane / FPW == k)
+                mine += (int64_t)((tot >> (16 * (lane % FPW))) & (W)0xffff);
+        }
+    }
+    if (lane < 2 * PART_NPIV_MAX) wsum[wv][lane] = lane < nf ? mine : 0;
+    __syncthreads();
+    if (t <= nf) {
+        int64_t c;
+        if (t < nf) {
+            c = wsum[0][t] + wsum[1][t] + wsum[2][t] + wsum[3][t];
+        } else {            // the last bucket: what is left of the block's keys
+            const int64_t lo = tile0 * PART_TILE;
+            const int64_t hi = tile1 * PART_TILE < n ? tile1 * PART_TILE : n;
+            c = hi - lo;
+            for (int f = 0; f < nf; ++f)
+                c -= wsum[0][f] + wsum[1][f] + wsum[2][f] + wsum[3][f];
+        }
+        counts[(int64_t)t * gridDim.x + blockIdx.x] = c;
+    }
+}
+
+// one block: base[b][blk] = (keys of the buckets below b) + (keys of bucket b
+// in the blocks before blk); totals[b] = the keys of bucket b
+__global__ __launch_bounds__(256) void part_scan_k(
+    const int64_t *__restrict__ counts, int64_t *__restrict__ base,
+    int64_t *__restrict__ totals, int nblocks, int nb) {
+    __shared__ unsigned long long wsum[2][4];
+    const int t = threadIdx.x, w = t >> 6, lane = t & 63;
+    const int per = (nblocks + 255) / 256;
+    const int lo = t * per < nblocks ? t * per : nblocks;
+    const int hi = lo + per < nblocks ? lo + per : nblocks;
+    unsigned long long carry = 0;
+    for (int b = 0; b < nb; ++b) {
+        const int64_t *row = counts + (int64_t)b * nblocks;
+        unsigned long long s = 0;
+        for (int i = lo; i < hi; ++i) s += (unsigned long long)row[i];
+        const unsigned long long x = sort_wave_incl(s, lane);
+        if (lane == 63) wsum[b & 1][w] = x;
+        __syncthreads();
+        unsigned long long run = carry + x - s, tot = 0;
+        for (int k = 0; k < 4; ++k) {
+            run += k < w ? wsum[b & 1][k] : 0ull;
+            tot += wsum[b & 1][k];
+        }
+        int64_t *orow = base + (int64_t)b * nblocks;
+        for (int i = lo; i < hi; ++i) {
+            orow[i] = (int64_t)run;
+            run += (unsigned long long)row[i];
+        }
+        if (t == 0) totals[b] = (int64_t)tot;
+        carry += tot;
+    }
+}
+
+template <typename T, typename W, int NW, int PMAX>
+__global__ __launch_bounds__(256) void part_scatter_k(
+    const SortU<T> *__restrict__ kin, SortU<T> *__restrict__ kout,
+    const int64_t *__restrict__ vin, int64_t *__restrict__ vout, int64_t val0,
+    int64_t n, int64_t tpb, int64_t ntiles, int vec, PartPivots pv, int npiv,
+    const int64_t *__restrict__ base) {
+    __shared__ W wtot[2][4][NW];                // double-buffered: one
+    __shared__ int64_t gbase[2][2 * PMAX + 1];  // barrier a tile
+    const int t = threadIdx.x, wv = t >> 6, lane = t & 63;
+    const int nf = 2 * npiv;
+    if (t <= nf) gbase[0][t] = base[(int64_t)t * gridDim.x + blockIdx.x];
+    const int64_t tile0 = (int64_t)blockIdx.x * tpb;
+    const int64_t tile1 = tile0 + tpb < ntiles ? tile0 + tpb : ntiles;
+    int buf = 0;
+    for (int64_t tile = tile0; tile < tile1; ++tile, buf ^= 1) {
+        SortU<T> raw[PART_KPL];
+        uint8_t bk[PART_KPL];
+        W w[NW], before[NW], tt[NW];
+        const int64_t tbase = tile * PART_TILE;
+        part_tile<T, W, NW, PMAX>(kin, n, tbase, t, vec != 0, pv, npiv, raw,
+                                  bk, w);
+#pragma unroll
+        for (int k = 0; k < NW; ++k) {
+            const W x = part_wave_incl<W>(w[k], lane);
+            before[k] = x - w[k];
+            if (lane == 63) wtot[buf][wv][k] = x;
+        }
+        __syncthreads();        // also orders gbase[buf] before its readers
+#pragma unroll
+        for (int k = 0; k < NW; ++k) {
+            tt[k] = 0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const W s = wtot[buf][q][k];
+                before[k] += q < wv ? s : (W)0;
+                tt[k] += s;
+            }
+        }
+        if (t <= nf) {          // the bases of the next tile
+            const int64_t left = n - tbase;
+            const int nvalid = left < PART_TILE ? (int)left : (int)PART_TILE;
+            const int c = t < nf ? part_field<W, NW>(tt, t)
+                                 : nvalid - part_field_sum<W, NW>(tt);
+            gbase[buf ^ 1][t] = gbase[buf][t] + c;
+        }
+        const int64_t i0 = tbase + (int64_t)t * PART_KPL;
+#pragma unroll
+        for (int j = 0; j < PART_KPL; ++j) {
+            if (i0 + j < n) {
+                const int f = bk[j];
+                // the valid keys of a tile are a prefix of it: t * KPL + j of
+                // them come before this one
+                const int pos =
+                    f < nf ? part_field<W, NW>(before, f)
+                           : t * PART_KPL + j - part_field_sum<W, NW>(before);
+                const int64_t dst = gbase[buf][f] + pos;
+                if (kout) kout[dst] = raw[j];
+                if (vout) vout[dst] = vin ? vin[i0 + j] : val0 + i0 + j;
+                part_add<W, NW>(before, f, nf);
+            }
+        }
+    }
+}
+
+template <typename T, typename W, int NW, int PMAX>
+int part_launch(hipStream_t st, const void *in, void *out, const void *vals_in,
+                int64_t val0, void *vals_out, int64_t n, int npiv,
+                const PartPivots &pv, void *scratch) {
+    using U = SortU<T>;
+    const PartPlan p = part_plan(n);
+    const int nb = 2 * npiv + 1;
+    int64_t *counts = static_cast<int64_t *>(scratch);
+    int64_t *base = counts + (int64_t)nb * p.nblocks;
+    int64_t *totals = base + (int64_t)nb * p.nblocks;
+    const int vec = reinterpret_cast<uintptr_t>(in) % 16 == 0;
+    part_count_k<T, W, NW, PMAX><<<p.nblocks, 256, 0, st>>>(
+        static_cast<const U *>(in), n, p.tpb, p.ntiles, vec, pv, npiv, counts);
+    part_scan_k<<<1, 256, 0, st>>>(counts, base, totals, p.nblocks, nb);
+    part_scatter_k<T, W, NW, PMAX><<<p.nblocks, 256, 0, st>>>(
+        static_cast<const U *>(in), static_cast<U *>(out),
+        static_cast<const int64_t *>(vals_in),
+        static_cast<int64_t *>(vals_out), val0, n, p.tpb, p.ntiles, vec, pv,
+        npiv, base);
+    return launched("rt_partition");
+}
+
+template <typename T>
+int part_run(hipStream_t st, const void *in, void *out, const void *vals_in,
+             int64_t val0, void *vals_out, int64_t n, int npiv,
+             const PartPivots &pv, void *scratch) {
+    if (npiv == 1)
+        return part_launch<T, uint32_t, 1, 1>(st, in, out, vals_in, val0,
+                                              vals_out, n, npiv, pv, scratch);
+    if (npiv <= 4)
+        return part_launch<T, uint64_t, 2, 4>(st, in, out, vals_in, val0,
+                                              vals_out, n, npiv, pv, scratch);
+    return part_launch<T, uint64_t, 4, 8>(st, in, out, vals_in, val0,
+                                          vals_out, n, npiv, pv, scratch);
+}
+
+}  // namespace
+
+extern "C" int rt_partition_geometry(int *block, int *keys_per_lane,
+                                     int *grid_cap, int *npiv_max) {
+    if (block) *block = PART_BLOCK;
+    if (keys_per_lane) *keys_per_lane = PART_KPL;
+    if (grid_cap) *grid_cap = PART_GRID_CAP;
+    if (npiv_max) *npiv_max = PART_NPIV_MAX;
+    return 0;
+}
+
+extern "C" int64_t rt_partition_scratch(int64_t n, int npiv) {
+    if (n < 0 || n >= (1LL << 40)) return -1;
+    if (npiv < 1 || npiv > PART_NPIV_MAX) return -1;
+    return part_scratch_bytes(n, npiv);
+}
+
+extern "C" int rt_partition(uintptr_t stream, const void *in, void *out,
+                            const void *vals_in, int64_t val0, void *vals_out,
+                            int64_t n, int dtype, int npiv,
+                            const uint64_t *pivots, void *scratch,
+                            int64_t scratch_bytes, int64_t *bucket_counts) {
+    const char *who = "rt_partition";
+    if (dtype < RT_F64 || dtype > RT_U8) return fail(who, "bad dtype");
+    if (n < 0) return fail(who, "negative n");
+    if (n >= (1LL << 40)) return fail(who, "n out of range");
+    if (npiv < 1 || npiv > PART_NPIV_MAX)
+        return fail(who, "npiv out of range");
+    if (!pivots) return fail(who, "NULL pivots");
+    const int width = 8 * dtype_size(dtype);
+    PartPivots pv;
+    for (int q = 0; q < PART_NPIV_MAX; ++q) pv.p[q] = 0;
+    for (int q = 0; q < npiv; ++q) {
+        if (width < 64 && (pivots[q] >> width) != 0)
+            return fail(who, "pivots: bits above the key width");
+        if (q && pivots[q] <= pivots[q - 1])
+            return fail(who, "pivots not distinct and ascending");
+        pv.p[q] = pivots[q];
+    }
+    if (n == 0) {
+        if (bucket_counts)
+            for (int b = 0; b < 2 * npiv + 1; ++b) bucket_counts[b] = 0;
+        return 0;
+    }
+    if (!in) return fail(who, "NULL in");
+    if (!out && !vals_out) return fail(who, "NULL out and vals_out");
+    if (!scratch) return fail(who, "NULL scratch");
+    if (reinterpret_cast<uintptr_t>(scratch) & 15)
+        return fail(who, "scratch not 16-byte aligned");
+    if (scratch_bytes < part_scratch_bytes(n, npiv))
+        return fail(who, "scratch_bytes too small (rt_partition_scratch)");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (dtype_dispatch<7>(who, dtype, [&](auto t) {
+            return part_run<decltype(t)>(st, in, out, vals_in, val0, vals_out,
+                                         n, npiv, pv, scratch);
+        }))
+        return 1;
+    if (!bucket_counts) return 0;
+    const PartPlan p = part_plan(n);
+    const int nb = 2 * npiv + 1;
+    HIP_CHECK(hipMemcpyAsync(
+        bucket_counts,
+        static_cast<int64_t *>(scratch) + (int64_t)2 * nb * p.nblocks,
+        nb * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    return 0;
+}

@@ -120,6 +120,11 @@ _RT_ABI = {
     "rt_searchsorted_geometry": (_int, [ctypes.POINTER(_int),
                                         ctypes.POINTER(_int), _p64,
                                         ctypes.POINTER(_int)]),
+    "rt_partition": (_int, [_sz, _vp, _vp, _vp, _i64, _vp, _i64, _int, _int,
+                            ctypes.POINTER(ctypes.c_uint64), _vp, _i64,
+                            _p64]),
+    "rt_partition_scratch": (_i64, [_i64, _int]),
+    "rt_partition_geometry": (_int, [ctypes.POINTER(_int)] * 4),
     "rt_stream_sync": (_int, [_sz]),
     "rt_device_sync": (_int, []),
     "rt_event_create": (_int, [_pvp]),
@@ -205,6 +210,17 @@ def searchsorted_geometry(lib):
                                  ctypes.byref(cap))
     return {"block": blk.value, "fence": fence.value, "grid_cap": cap.value,
             "lds_max": {1 << k: int(lmax[k]) for k in range(4)}}
+
+
+def partition_geometry(lib):
+    """rt_partition_geometry as a dict (host arithmetic; needs no GPU).
+    `tile` is block x keys_per_lane."""
+    vals = [ctypes.c_int() for _ in range(4)]
+    lib.rt_partition_geometry(*[ctypes.byref(v) for v in vals])
+    geo = dict(zip(("block", "keys_per_lane", "grid_cap", "npiv_max"),
+                   (v.value for v in vals)))
+    geo["tile"] = geo["block"] * geo["keys_per_lane"]
+    return geo
 
 
 def _hb_arg_chunks(nd, axis, nout, K):
@@ -1420,6 +1436,36 @@ class HipBackend:
             ctypes.c_void_p(spl.data_ptr()), m,
             ctypes.c_void_p(out.data_ptr())), "rt_sort_bounds")
         return out.cpu().numpy()
+
+    def split_run(self, keys, vals, val0, pivots, want_keys, want_vals,
+                  want_counts=True):
+        """The split_run hook of ramba_amd/sorting.py on rt_partition.
+        Without want_counts the bucket sizes are not read back (None) and the
+        call does not synchronise."""
+        torch = self.torch
+        n, npiv = int(keys.numel()), len(pivots)
+        out_k = torch.empty_like(keys) if want_keys else None
+        out_v = torch.empty(n, dtype=torch.int64, device="cuda") \
+            if want_vals else None
+        counts = (ctypes.c_int64 * (2 * npiv + 1))()
+        keys = keys.contiguous()
+        if vals is not None:
+            vals = vals.contiguous()
+        nbytes = int(self.lib.rt_partition_scratch(max(n, 1), npiv))
+        scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8,
+                              device="cuda")
+        self._check(self.lib.rt_partition(
+            self._stream(), ctypes.c_void_p(keys.data_ptr()) if n else None,
+            ctypes.c_void_p(out_k.data_ptr()) if want_keys and n else None,
+            ctypes.c_void_p(vals.data_ptr()) if vals is not None and n
+            else None, int(val0),
+            ctypes.c_void_p(out_v.data_ptr()) if want_vals and n else None,
+            n, RT_DTYPE[str(keys.dtype).replace("torch.", "")], npiv,
+            (ctypes.c_uint64 * npiv)(*[int(p) for p in pivots]),
+            ctypes.c_void_p(scratch.data_ptr()), nbytes,
+            counts if want_counts else None), "rt_partition")
+        return out_k, out_v, (np.array(counts, dtype=np.int64)
+                              if want_counts else None)
 
     # -- unique / searchsorted (runtime.unique_op, searchsorted_op) -----------
     #

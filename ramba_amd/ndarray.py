@@ -1576,6 +1576,99 @@ ndarray._ARRAY_FUNC.update({
 })
 
 
+# -- partition / argpartition on runtime.partition_op: a radix select finds
+#    the keys at the wanted ranks and one stable split moves the data around
+#    them (rt_partition); nothing is sorted.  Sync points, like sort. --------
+
+def _partition_kth(kth, length, bounded):
+    """NumPy's treatment of kth: the wrapped positions as Python ints, or
+    NumPy's own error.  NumPy checks no bounds on an empty array."""
+    kth = np.asarray(kth)
+    if kth.dtype.kind not in "iu":
+        raise TypeError("Partition index must be integer")
+    if kth.ndim > 1:
+        raise ValueError("object too deep for desired array")
+    out = []
+    for k in kth.reshape(-1).tolist():
+        k = k + length if k < 0 else k
+        if bounded and not 0 <= k < length:
+            raise ValueError(f"kth(={k}) out of bounds ({length})")
+        out.append(k)
+    return out
+
+
+def _partitioned(a, kth, axis, kind, order, want_index, name):
+    if not isinstance(a, ndarray):      # host data: NumPy's
+        return getattr(np, name)(a, kth, axis=axis, kind=kind, order=order)
+    if order is not None:
+        raise NotImplementedError(
+            f"{name}: order= (structured dtypes) is not supported")
+    if a.dtype.kind == "c":
+        raise NotImplementedError(f"{name}: complex input is not supported")
+    if a.ndim > 4:
+        raise NotImplementedError(
+            f"{name} supports arrays of up to 4 dimensions")
+    if axis is None:
+        if a.ndim != 1:
+            a = a.ravel()
+        axis = 0
+    axis = operator.index(axis)
+    nd = a.ndim
+    if not (-nd <= axis < nd):
+        raise np.exceptions.AxisError(axis, nd)
+    axis = axis + nd if axis < 0 else axis
+    ranks = sorted(set(_partition_kth(kth, a.shape[axis], a.size > 0)))
+    if a.size == 0:
+        return zeros(a.shape, dtype=np.int64 if want_index else a.dtype)
+    from .sorting import NPIV_MAX
+    if nd != 1 or len(ranks) > NPIV_MAX:
+        # a sorted line is a valid partition of it
+        return _sorted(a, axis, None, None, want_index,
+                       "argsort" if want_index else "sort")
+    rt = deferred.get_runtime()
+    src = _gemm_operand(a, a.dtype, rt)
+    deferred.flush()
+    return _from_bd(rt.partition_op(src, ranks, want_index))
+
+
+def partition(a, kth, axis=-1, kind="introselect", order=None):
+    """numpy.partition for ramba arrays.  A 1-D array (or axis=None) is split
+    about the elements at the kth ranks: what sorts before them, what equals
+    them and what lies between them, each group in input order (a defined,
+    repeatable result; NaN last, as NumPy).  More than 8 distinct kth, and
+    N-D input along an axis, come back fully sorted along that axis, which
+    satisfies the contract.  `kind` is ignored; order= and complex input are
+    not supported."""
+    return _partitioned(a, kth, axis, kind, order, False, "partition")
+
+
+def argpartition(a, kth, axis=-1, kind="introselect", order=None):
+    """numpy.argpartition for ramba arrays: the int64 indices that
+    `partition` would move into place (of the flattened array for
+    axis=None)."""
+    return _partitioned(a, kth, axis, kind, order, True, "argpartition")
+
+
+def _nd_partition(self, kth, axis=-1, kind="introselect", order=None):
+    """In place: the partitioned result is assigned back."""
+    if axis is None:
+        raise TypeError("'NoneType' object cannot be interpreted as an "
+                        "integer")
+    self[()] = partition(self, kth, axis=axis, kind=kind, order=order)
+
+
+ndarray.partition = _nd_partition
+ndarray.argpartition = lambda self, kth, axis=-1, kind="introselect", \
+    order=None: argpartition(self, kth, axis=axis, kind=kind, order=order)
+ndarray._ARRAY_FUNC.update({
+    "partition": lambda a, kth, axis=-1, kind="introselect", order=None, **kw:
+        partition(a, kth, axis=axis, kind=kind, order=order),
+    "argpartition":
+        lambda a, kth, axis=-1, kind="introselect", order=None, **kw:
+        argpartition(a, kth, axis=axis, kind=kind, order=order),
+})
+
+
 # -- unique / searchsorted on runtime.unique_op / searchsorted_op.  unique
 #    ravels the array onto contiguous divisions through the engine (as sort
 #    with axis=None does), sorts it and compacts the runs; the inverse is a

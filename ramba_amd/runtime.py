@@ -1822,3 +1822,118 @@ def select_op(self, arr, ranks, skipna):
 
 
 Runtime.select_op = select_op
+
+
+# ---------------------------------------------------------------------------
+# partition / argpartition (numpy.partition, numpy.argpartition; the
+# reference has neither): select, then split.  One select_op call finds the
+# canonical keys at the wanted ranks (NaNs are ranked last: a rank at or past
+# n - nan_count has the all-ones key); equal keys are merged into P distinct
+# ascending pivots.  The bucket of an element with key c is
+#     2 * (pivots < c) + (c is a pivot),
+# 2P + 1 buckets, and the result is the buckets in ascending order, each in
+# global input order: every element below the pivot of a rank comes before
+# that rank, every equal element fills a span that covers it, every greater
+# one follows.  Each rank splits its run with the split_run hook of
+# ramba_amd/sorting.py, the payload being the global index.  The 2P + 1 local
+# counts are allgathered; the global start of (bucket b, rank r) is the total
+# of the buckets below b plus the counts of b on the ranks before r.  The
+# result keeps the even contiguous divisions, so a rank cuts its bucket
+# segments at the owners' boundaries and the pieces travel with
+# backend.exchange, one message per pair of ranks, pieces in bucket order.  At
+# world 1 nothing is exchanged and the counts are not read back.
+# ---------------------------------------------------------------------------
+
+def partition_op(self, arr, kth, want_index):
+    """The constructed 1-D `arr` partitioned about the ranks `kth` (distinct
+    ints in [0, n)), or with want_index the int64 indices that do it, as a
+    bdarray on arr's divisions."""
+    from .sorting import NPIV_MAX, hooks_for
+    bd = arr.bdarray
+    assert len(bd.shape) == 1 and bd.shape[0] > 0 \
+        and arr.view.is_identity_for(bd.shape), "partition_op: 1-D, non-empty"
+    _on_contiguous(self, "partition_op", bd)
+    hooks = hooks_for(self.backend)
+    known = getattr(hooks, "sort_dtypes", None)     # None: any NumPy dtype
+    if known is not None and str(np.dtype(bd.dtype)) not in known:
+        raise NotImplementedError(
+            f"partition / argpartition: no kernel for dtype {bd.dtype}")
+    W, me, n = self.world, self.rank, int(bd.shape[0])
+    kth = sorted(set(int(k) for k in kth))
+    keys, _, nan = self.select_op(
+        arr, lambda m: [k for k in kth if k < m], True)
+    pivots = set(keys)
+    if kth[-1] >= n - nan:
+        pivots.add((1 << 8 * np.dtype(bd.dtype).itemsize) - 1)
+    pivots = sorted(pivots)
+    assert 1 <= len(pivots) <= NPIV_MAX, "partition_op: too many pivots"
+    core = self.core_box(bd, me)
+    start = 0 if core is None else int(core[0, 0])
+    skeys, sidx, counts = hooks.split_run(
+        hooks.local_run(bd, self), None, start, pivots, not want_index,
+        want_index, W > 1)
+    res = sidx if want_index else skeys
+    out_bd = self.new_result(
+        bd.shape, np.dtype(np.int64) if want_index else bd.dtype, bd.divisions)
+    if W > 1:
+        res = _partition_exchange(self, bd, res, counts)
+    if res.shape[0]:
+        self.backend.write_local_dense(out_bd, self, res)
+    self.backend.free_temps()
+    return out_bd
+
+
+def _partition_exchange(self, bd, res, counts):
+    """The rank's part of the global result: `res` is its split run, `counts`
+    its bucket sizes."""
+    import torch
+    W, me, nb = self.world, self.rank, len(counts)
+    allc = np.zeros((W, nb), dtype=np.int64)
+    for b in range(nb):
+        allc[:, b] = [int(c) for c in self.backend.allgather_scalars(
+            np.int64(counts[b]), np.int64)]
+    tot = allc.sum(axis=0)
+    gstart = (np.cumsum(tot) - tot)[None, :] + np.cumsum(allc, axis=0) - allc
+    spans = [_span(bd, r) for r in range(W)]
+
+    def pieces(r):
+        """Rank r's segments cut at the owners' boundaries, in bucket order:
+        (owner, offset in r's split run, global start, length)."""
+        out, off = [], 0
+        for b in range(nb):
+            g, ln = int(gstart[r, b]), int(allc[r, b])
+            for s in range(W):
+                lo, hi = max(g, spans[s][0]), min(g + ln, spans[s][1])
+                if hi > lo:
+                    out.append((s, off + lo - g, lo, hi - lo))
+            off += ln
+        return out
+
+    mine = pieces(me)
+    sends = []
+    for s in range(W):
+        parts = [res[o:o + ln] for d, o, _, ln in mine if d == s != me]
+        if parts:
+            sends.append((s, torch.cat(parts)))
+    inbound = {r: [(o, g, ln) for d, o, g, ln in
+                   (mine if r == me else pieces(r)) if d == me]
+               for r in range(W)}
+    recvs = [(r, res.new_empty((sum(ln for _, _, ln in inbound[r]),)))
+             for r in range(W) if r != me and inbound[r]]
+    if sends or recvs:
+        self.backend.exchange(sends, recvs)
+    got = dict(recvs)
+    k0, k1 = spans[me]
+    dest = res.new_empty((max(k1 - k0, 0),))
+    for r in range(W):
+        pos = 0
+        for o, g, ln in inbound[r]:
+            if r == me:
+                dest[g - k0:g - k0 + ln] = res[o:o + ln]
+            else:
+                dest[g - k0:g - k0 + ln] = got[r][pos:pos + ln]
+                pos += ln
+    return dest
+
+
+Runtime.partition_op = partition_op

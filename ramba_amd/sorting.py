@@ -17,6 +17,15 @@ own device, payloads and positions as int64:
     sort_bounds(run, splitters) -> int64 NumPy array
         for each splitter (a NumPy array of the keys' dtype) the number of
         keys of the sorted `run` that sort strictly before it.
+    split_run(keys, vals, val0, pivots, want_keys, want_vals,
+              want_counts=True) -> (keys, vals, counts)
+        the stable split of one dense run behind partition / argpartition:
+        `pivots` are at most NPIV_MAX distinct ascending canonical keys
+        (Python ints), the bucket of a key k is 2 * (pivots < canon(k)) +
+        (canon(k) is a pivot), and the result is the buckets in ascending
+        order, each in input order.  Payloads as in sort_run; counts is the
+        int64 NumPy array of the 2 * len(pivots) + 1 bucket sizes, which a
+        hook may leave out (None) when want_counts is false.
 
 The order is NumPy's stable sort order (include/ramba_sortkey.h): floats
 with -0.0 == +0.0 and every NaN equal and last, ties by position.
@@ -27,6 +36,8 @@ np.argsort(kind="stable").  The reference has no sort.
 """
 
 import numpy as np
+
+NPIV_MAX = 8        # pivots per split (PART_NPIV_MAX = SELECT_NQ_MAX)
 
 
 def hooks_for(backend):
@@ -85,3 +96,21 @@ class HostSort:
 
     def sort_bounds(self, run, splitters):
         return splitter_bounds(run.numpy(), splitters)
+
+    def split_run(self, keys, vals, val0, pivots, want_keys, want_vals,
+                  want_counts=True):
+        import torch
+        from .selection import canon
+        k = keys.numpy()
+        c = canon(k)
+        piv = np.array(pivots, dtype=c.dtype)
+        bucket = 2 * np.searchsorted(piv, c, side="left") + np.isin(c, piv)
+        order = np.argsort(bucket, kind="stable")
+        out_k = torch.from_numpy(k[order]) if want_keys else None
+        out_v = None
+        if want_vals:
+            out_v = torch.from_numpy(
+                (order + np.int64(val0)) if vals is None
+                else vals.numpy()[order])
+        counts = np.bincount(bucket, minlength=2 * len(pivots) + 1)
+        return out_k, out_v, counts.astype(np.int64)
