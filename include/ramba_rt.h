@@ -648,6 +648,62 @@ int64_t rt_partition_scratch(int64_t n, int npiv);
 int rt_partition_geometry(int *block, int *keys_per_lane, int *grid_cap,
                           int *npiv_max);
 
+/* groupby reductions — the reference's ndarray.groupby(dim, labels,
+ * num_groups).sum() / prod() / min() / max() / nanmean() (ramba.py:10290).
+ * rt_group_reduce reads a strided box of 1..4 axes at `in + in_off` (offset
+ * and strides in elements, any sign, zero allowed; dtype: any rt_dtype) whose
+ * axis `axis` carries one group label per row, given as a CSR on the device:
+ *   members  int32[shape[axis]]: the row numbers, stably sorted by label;
+ *   seg      int32[ngroups + 1]: group g owns members[seg[g] .. seg[g + 1]).
+ * out[.., g, ..] (extent ngroups on `axis`, out_strides in elements) receives
+ * the reduction of group g's rows, the identity for an empty group.
+ *   op       0 SUM, 1 PROD, 2 MIN, 3 MAX, 4 COUNT_VALID (the number of
+ *            non-NaN members).
+ *   out      SUM / PROD: the input's type for floats, int64 with wrap-around
+ *            for integers; MIN / MAX: the input's type (RT_U8 is bool:
+ *            identities 1 and 0); COUNT_VALID: int64.
+ *   skipna   a NaN counts as the identity.  Without it NaN propagates; float
+ *            MIN / MAX keep the first of two equal values.
+ * No atomics: the order in which a group's members are combined is fixed by
+ * the shape, the labels and the compiled-in constants, so the result is the
+ * same from run to run.  Regimes (rt_group_regime; see ramba_rt.cpp):
+ *   0 ROWS         another axis has the unit stride: lanes along it, a block
+ *                  per (group, tile), members staged through LDS member_tile
+ *                  at a time and combined in ascending order (a float SUM
+ *                  equals the sequential np.add.at bit for bit); 16-byte
+ *                  loads under the rule of rt_arg_flat_regime.
+ *   1 ROWS_SPLIT   ROWS with fewer than split_blocks (group, 256 outputs)
+ *                  pairs and shape[axis] >= 2 chunk + 1: member lists cut
+ *                  into chunks of `chunk` rows, partials combined in order by
+ *                  a second launch.
+ *   2 LINE_SELECT  the group axis has the unit stride, ngroups <= select_max:
+ *                  select_max compare-select register accumulators per lane,
+ *                  a shuffle tree, LDS, per-block partials combined in order.
+ *   3 LINE_GATHER  the same with more groups: a wave per (line, chunk of
+ *                  gather_chunk members), a shuffle tree, chunks in order.
+ * scratch: device memory, 16-byte aligned, of at least rt_group_scratch(..)
+ * bytes (0 in regime ROWS; NULL is then accepted).  in / members / seg are
+ * only read and must not overlap out or the scratch.
+ * Validated before any HIP call: nd, NULL shape / strides / out_strides,
+ * extents, axis, dtype, op, ngroups < 1 or >= 2^31, shape[axis] >= 2^31, a
+ * result beyond 2^46 elements, NULL in / members / seg / out / scratch with
+ * work to do, a misaligned scratch.  A zero extent returns 0 without
+ * launching.  rt_group_regime (-1 for bad arguments), rt_group_scratch (-1
+ * likewise) and rt_group_geometry (the compiled-in constants; any pointer may
+ * be NULL) are host arithmetic only. */
+int rt_group_reduce(uintptr_t stream, const void *in, int64_t in_off, int nd,
+                    const int64_t *shape, const int64_t *strides, int axis,
+                    int dtype, int op, int skipna, const void *members,
+                    const void *seg, int64_t ngroups, void *out,
+                    const int64_t *out_strides, void *scratch);
+int64_t rt_group_scratch(int nd, const int64_t *shape, const int64_t *strides,
+                         int axis, int dtype, int op, int64_t ngroups);
+int rt_group_regime(int nd, const int64_t *shape, const int64_t *strides,
+                    int axis, int dtype, int64_t ngroups);
+int rt_group_geometry(int *block, int *member_tile, int *chunk,
+                      int *split_blocks, int *select_max, int *select_blocks,
+                      int *gather_chunk, int *grid_cap);
+
 int rt_stream_sync(uintptr_t stream);
 int rt_device_sync(void);
 

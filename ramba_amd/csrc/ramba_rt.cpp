@@ -14,8 +14,10 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <limits>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -5357,4 +5359,802 @@ extern "C" int rt_partition(uintptr_t stream, const void *in, void *out,
         nb * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
     return 0;
+}
+
+// ---------------------------------------------------------------------------
+// groupby reductions (the reference's RambaGroupby, ramba.py:10290-10607): a
+// keyed reduction of values.  The rows of one axis of a strided box carry a
+// group label each; out[.., g, ..] is the reduction over the rows of group g.
+// The host hands the labels over as a CSR: `members`, the row numbers stably
+// sorted by label, and `seg`, ngroups + 1 offsets into it (both int32).  No
+// kernel uses an atomic: every output is combined in an order fixed by the
+// shape, the labels and the constants below, so a float result has the same
+// bits from run to run.
+//
+// Accumulators: floats in their own type; SUM / PROD of integers in int64
+// with wrap-around; MIN / MAX in the element type (RT_U8 is bool: identities
+// 1 and 0); COUNT_VALID, the int64 number of non-NaN members, is a SUM of
+// (x == x).  skipna replaces a NaN by the identity.  Float MIN / MAX
+// propagate NaN and keep the first of two equal values, as the scalar loops
+// of np.minimum.at / np.maximum.at do.
+//
+// Regimes (rt_group_regime), chosen from the strides:
+//   ROWS         another axis has the unit stride (or no axis has).  Lanes
+//                lie along that axis (16-byte loads under the rule of
+//                rt_arg_flat_regime, else element loads); a block owns one
+//                group and a tile of 256 lanes, which is several short rows
+//                of the remaining axes when the lane axis is shorter.  The
+//                group's member rows are staged through LDS GROUP_MEMBER_TILE
+//                at a time as element offsets, and every lane walks them in
+//                ascending order, four loads in flight, combining in order:
+//                each input byte is read once, and a float SUM equals the
+//                sequential np.add.at bit for bit.
+//   ROWS_SPLIT   ROWS when ngroups x tiles cannot fill the chip and the axis
+//                is long: a member list is cut into chunks of GROUP_CHUNK
+//                rows, a block reduces one chunk into a partial, and a second
+//                launch combines a group's partials in ascending order.
+//   LINE_SELECT  the group axis has the unit stride (1-D included) and
+//                ngroups <= GROUP_SELECT_MAX.  A small launch turns the CSR
+//                back into one label byte per row.  A block reads a span of a
+//                line with its labels, each lane keeps GROUP_SELECT_MAX
+//                register accumulators and combines into each the value or
+//                the identity (compare-select, no dynamic register index);
+//                lanes merge in a shuffle tree, waves through LDS, and a
+//                second launch combines the blocks of a line in ascending
+//                order.
+//   LINE_GATHER  as above with more groups: one wave per (line, chunk of
+//                GROUP_GATHER_CHUNK members) gathers x[line, members[j]], j
+//                ascending per lane, merges in a shuffle tree; a second
+//                launch combines the chunks in order.  Cache lines shared
+//                between groups are read once per group.
+// Chunk c of group g owns the partial slot seg[g] / chunk + g + c: at most
+// K / chunk + ngroups slots, found again from a slot number by a binary
+// search on seg.  Member rows and seg offsets are clamped into range before
+// use, so a malformed CSR gives wrong numbers, never a wild address.
+// ---------------------------------------------------------------------------
+
+namespace {
+
+enum { GROUP_SUM = 0, GROUP_PROD = 1, GROUP_MIN = 2, GROUP_MAX = 3,
+       GROUP_COUNT_VALID = 4 };
+enum { GROUP_ROWS = 0, GROUP_ROWS_SPLIT = 1, GROUP_LINE_SELECT = 2,
+       GROUP_LINE_GATHER = 3 };
+enum {
+    GROUP_BLOCK = 256,
+    GROUP_MEMBER_TILE = 256,      // member rows staged in LDS at a time
+    GROUP_CHUNK = 512,            // rows per partial, ROWS_SPLIT
+    GROUP_SPLIT_BLOCKS = 1024,    // split below this many (group, tile) pairs
+    GROUP_SELECT_MAX = 16,        // register accumulators per lane
+    GROUP_SELECT_BLOCKS = 2048,   // blocks of LINE_SELECT, over all lines
+    GROUP_GATHER_CHUNK = 1024,    // members per wave, LINE_GATHER
+    GROUP_GRID_CAP = 1 << 16      // blocks per launch; work items beyond loop
+};
+
+// combining two accumulators of type A under SUM / PROD / MIN / MAX
+template <typename A, int OP>
+struct GroupAcc {
+    static constexpr bool F = std::is_floating_point<A>::value;
+
+    static __host__ __device__ __forceinline__ A identity() {
+        if constexpr (OP == GROUP_SUM) {
+            return A(0);
+        } else if constexpr (OP == GROUP_PROD) {
+            return A(1);
+        } else if constexpr (F) {
+            return OP == GROUP_MIN ? A(__builtin_inf()) : A(-__builtin_inf());
+        } else if constexpr (std::is_same<A, uint8_t>::value) {
+            return OP == GROUP_MIN ? A(1) : A(0);
+        } else {
+            return OP == GROUP_MIN ? std::numeric_limits<A>::max()
+                                   : std::numeric_limits<A>::min();
+        }
+    }
+
+    static __device__ __forceinline__ A comb(A a, A b) {
+        if constexpr (OP == GROUP_SUM) {
+            if constexpr (F) return a + b;
+            else return (A)((uint64_t)a + (uint64_t)b);
+        } else if constexpr (OP == GROUP_PROD) {
+            if constexpr (F) return a * b;
+            else return (A)((uint64_t)a * (uint64_t)b);
+        } else if constexpr (OP == GROUP_MIN) {
+            if constexpr (F) return (a <= b || a != a) ? a : b;
+            else return b < a ? b : a;
+        } else {
+            if constexpr (F) return (a >= b || a != a) ? a : b;
+            else return b > a ? b : a;
+        }
+    }
+};
+
+// an element of type T as an accumulator of reduction OP
+template <typename T, int OP>
+struct GroupRed {
+    static constexpr bool F = std::is_floating_point<T>::value;
+    static constexpr int AOP = OP == GROUP_COUNT_VALID ? GROUP_SUM : OP;
+    using A = std::conditional_t<
+        OP == GROUP_COUNT_VALID || (!F && OP <= GROUP_PROD), int64_t, T>;
+    using Acc = GroupAcc<A, AOP>;
+
+    static __device__ __forceinline__ A lift(T x, int skipna) {
+        if constexpr (OP == GROUP_COUNT_VALID) {
+            if constexpr (F) return (A)(x == x);
+            else return A(1);
+        } else {
+            if constexpr (F)
+                if (skipna && x != x) return Acc::identity();
+            return (A)x;
+        }
+    }
+};
+
+struct GroupArgs {
+    int64_t K, sK, osG;      // group axis: rows, input and output stride
+    int64_t ext[3], str[3], ostr[3];   // the other axes, slowest first; in
+                                       // ROWS [2] is the lane axis
+    int64_t P;               // ext[0] * ext[1] * ext[2]
+    int64_t ngroups;
+    int64_t items;           // work items of the launch
+    int64_t nslots;          // ROWS_SPLIT / LINE_GATHER: partial slots
+    int64_t nu, tiles_in, tiles;   // ROWS: lane-axis units, tiles along the
+                                   // lane axis, tiles per group
+    int64_t bpl, span;       // LINE_SELECT: blocks per line, rows per block
+    int lpr_shift;           // ROWS: a block is (256 >> s) rows of (1 << s)
+    int split, skipna;
+};
+
+// how a second launch finds the partials of output (g, p):
+// part[(base + c) * slot_stride + p * p_stride + g * g_stride], c ascending
+struct GroupFinArgs {
+    int64_t chunk;           // > 0: base and count from seg (slot scheme)
+    int64_t count;           // chunk == 0: a fixed count, base 0
+    int64_t slot_stride, p_stride, g_stride;
+};
+
+__device__ __forceinline__ int64_t group_seg(const int32_t *seg, int64_t g,
+                                             int64_t K) {
+    const int64_t s = seg[g];
+    return s < 0 ? 0 : s > K ? K : s;
+}
+
+__device__ __forceinline__ int64_t group_member(const int32_t *members,
+                                                int64_t j, int64_t K) {
+    const int64_t m = members[j];
+    return m < 0 ? 0 : m >= K ? K - 1 : m;
+}
+
+// Slot s -> its group g and member range [m0, m1); false for a slot that no
+// chunk owns.  base(g) = seg[g] / chunk + g grows strictly with g and
+// base(0) = 0, so the owner is the last g with base(g) <= s.
+__device__ __forceinline__ bool group_slot(const int32_t *seg,
+                                           int64_t ngroups, int64_t K,
+                                           int64_t chunk, int64_t s,
+                                           int64_t &g, int64_t &m0,
+                                           int64_t &m1) {
+    int64_t lo = 0, hi = ngroups - 1;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if (group_seg(seg, mid, K) / chunk + mid <= s)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    g = lo;
+    const int64_t s0 = group_seg(seg, g, K), s1 = group_seg(seg, g + 1, K);
+    const int64_t c = s - (s0 / chunk + g);
+    m0 = s0 + c * chunk;
+    if (c < 0 || m0 >= s1) return false;
+    m1 = m0 + chunk < s1 ? m0 + chunk : s1;
+    return true;
+}
+
+// position p of the three non-group axes -> input and output offsets
+__device__ __forceinline__ void group_line_off(const GroupArgs &a, int64_t p,
+                                               int64_t &in_off,
+                                               int64_t &out_off) {
+    const int64_t q = p / a.ext[2], i2 = p - q * a.ext[2];
+    const int64_t i0 = q / a.ext[1], i1 = q - i0 * a.ext[1];
+    in_off = i0 * a.str[0] + i1 * a.str[1] + i2 * a.str[2];
+    out_off = i0 * a.ostr[0] + i1 * a.ostr[1] + i2 * a.ostr[2];
+}
+
+template <typename A>
+__device__ __forceinline__ A group_shfl_down(A v, int d) {
+    if constexpr (sizeof(A) == 8) {
+        uint32_t w[2];
+        __builtin_memcpy(w, &v, 8);
+        w[0] = __shfl_down(w[0], d);
+        w[1] = __shfl_down(w[1], d);
+        __builtin_memcpy(&v, w, 8);
+        return v;
+    } else if constexpr (sizeof(A) == 4) {
+        uint32_t w;
+        __builtin_memcpy(&w, &v, 4);
+        w = __shfl_down(w, d);
+        __builtin_memcpy(&v, &w, 4);
+        return v;
+    } else {
+        return (A)__shfl_down((int)v, d);
+    }
+}
+
+// lane 0 ends with the wave's 64 values combined in a fixed binary tree
+template <typename Acc, typename A>
+__device__ __forceinline__ A group_wave_tree(A v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1)
+        v = Acc::comb(v, group_shfl_down<A>(v, d));
+    return v;
+}
+
+// one load unit (uint4 of 16 / sizeof(T) elements, or one element) combined
+// into the lane's accumulators, element by element
+template <typename T, int OP, typename L>
+__device__ __forceinline__ void group_rows_add(
+    typename GroupRed<T, OP>::A *acc, const L &unit, int skipna) {
+    using R = GroupRed<T, OP>;
+    constexpr int V = sizeof(L) / sizeof(T);
+    T e[V];
+    __builtin_memcpy(e, &unit, sizeof(L));
+#pragma unroll
+    for (int i = 0; i < V; ++i)
+        acc[i] = R::Acc::comb(acc[i], R::lift(e[i], skipna));
+}
+
+template <typename T, int OP, bool VEC>
+__global__ __launch_bounds__(256) GEMM_NO_PK_F32 void group_rows_kernel(
+    const T *__restrict__ in, GroupArgs a,
+    const int32_t *__restrict__ members, const int32_t *__restrict__ seg,
+    typename GroupRed<T, OP>::A *__restrict__ out,
+    typename GroupRed<T, OP>::A *__restrict__ part) {
+    using R = GroupRed<T, OP>;
+    using A = typename R::A;
+    using L = std::conditional_t<VEC, uint4, T>;
+    constexpr int V = sizeof(L) / sizeof(T);
+    __shared__ int64_t goff[GROUP_MEMBER_TILE];
+    const int tid = threadIdx.x;
+    const int64_t u_in = tid & ((1 << a.lpr_shift) - 1);
+    const int64_t r_in = tid >> a.lpr_shift;
+    const int64_t nouter = a.ext[0] * a.ext[1];
+
+    for (int64_t w = blockIdx.x; w < a.items; w += gridDim.x) {
+        const int64_t s = w / a.tiles, t = w - s * a.tiles;
+        int64_t g = s, m0, m1;
+        if (a.split) {
+            if (!group_slot(seg, a.ngroups, a.K, GROUP_CHUNK, s, g, m0, m1))
+                continue;                       // the whole block, no barrier
+        } else {
+            m0 = group_seg(seg, g, a.K);
+            m1 = group_seg(seg, g + 1, a.K);
+        }
+        const int64_t to = t / a.tiles_in, ti = t - to * a.tiles_in;
+        const int64_t iu = (ti << a.lpr_shift) + u_in;
+        const int64_t o = (to << (8 - a.lpr_shift)) + r_in;
+        const bool live = iu < a.nu && o < nouter;
+        const int64_t i0 = o / a.ext[1], i1 = o - i0 * a.ext[1];
+        const T *base = in + i0 * a.str[0] + i1 * a.str[1]
+                        + iu * V * a.str[2];
+        A acc[V];
+#pragma unroll
+        for (int i = 0; i < V; ++i) acc[i] = R::Acc::identity();
+
+        for (int64_t tm = m0; tm < m1; tm += GROUP_MEMBER_TILE) {
+            const int n = (int)(m1 - tm < GROUP_MEMBER_TILE
+                                    ? m1 - tm : GROUP_MEMBER_TILE);
+            __syncthreads();                    // the last tile is used up
+            for (int j = tid; j < n; j += GROUP_BLOCK)
+                goff[j] = group_member(members, tm + j, a.K) * a.sK;
+            __syncthreads();
+            if (live) {
+                int j = 0;
+                for (; j + 4 <= n; j += 4) {
+                    const L x0 = *reinterpret_cast<const L *>(base + goff[j]);
+                    const L x1 =
+                        *reinterpret_cast<const L *>(base + goff[j + 1]);
+                    const L x2 =
+                        *reinterpret_cast<const L *>(base + goff[j + 2]);
+                    const L x3 =
+                        *reinterpret_cast<const L *>(base + goff[j + 3]);
+                    group_rows_add<T, OP, L>(acc, x0, a.skipna);
+                    group_rows_add<T, OP, L>(acc, x1, a.skipna);
+                    group_rows_add<T, OP, L>(acc, x2, a.skipna);
+                    group_rows_add<T, OP, L>(acc, x3, a.skipna);
+                }
+                for (; j < n; ++j) {
+                    const L x0 = *reinterpret_cast<const L *>(base + goff[j]);
+                    group_rows_add<T, OP, L>(acc, x0, a.skipna);
+                }
+            }
+        }
+        if (!live) continue;                    // no barrier below
+        if (a.split) {
+            A *p = part + s * a.P + o * a.ext[2] + iu * V;
+#pragma unroll
+            for (int i = 0; i < V; ++i) p[i] = acc[i];
+        } else {
+            A *p = out + g * a.osG + i0 * a.ostr[0] + i1 * a.ostr[1]
+                   + iu * V * a.ostr[2];
+#pragma unroll
+            for (int i = 0; i < V; ++i) p[i * a.ostr[2]] = acc[i];
+        }
+    }
+}
+
+// LINE_SELECT, launch 1: label byte of every row from the CSR
+__global__ __launch_bounds__(256) void group_labels_kernel(
+    const int32_t *__restrict__ members, const int32_t *__restrict__ seg,
+    int64_t K, int ngroups, uint8_t *__restrict__ lab) {
+    const int64_t S = (int64_t)gridDim.x * GROUP_BLOCK;
+    for (int64_t j = (int64_t)blockIdx.x * GROUP_BLOCK + threadIdx.x; j < K;
+         j += S) {
+        int g = 0;      // the last group whose segment starts at or before j
+        for (int q = 1; q < ngroups; ++q) g += group_seg(seg, q, K) <= j;
+        lab[group_member(members, j, K)] = (uint8_t)g;
+    }
+}
+
+template <typename T, int OP>
+__device__ __forceinline__ void group_select_add(
+    typename GroupRed<T, OP>::A *acc, T x, int label, int skipna) {
+    using R = GroupRed<T, OP>;
+    const typename R::A v = R::lift(x, skipna);
+#pragma unroll
+    for (int g = 0; g < GROUP_SELECT_MAX; ++g)
+        acc[g] = R::Acc::comb(acc[g], label == g ? v : R::Acc::identity());
+}
+
+template <typename T, int OP, bool VEC>
+__global__ __launch_bounds__(256) GEMM_NO_PK_F32 void group_select_kernel(
+    const T *__restrict__ in, GroupArgs a, const uint8_t *__restrict__ lab,
+    typename GroupRed<T, OP>::A *__restrict__ part) {
+    using R = GroupRed<T, OP>;
+    using A = typename R::A;
+    using L = std::conditional_t<VEC, uint4, T>;
+    constexpr int V = sizeof(L) / sizeof(T);
+    constexpr int NG = GROUP_SELECT_MAX;
+    __shared__ A wave_acc[GROUP_BLOCK / 64][NG];
+    const int tid = threadIdx.x;
+
+    for (int64_t w = blockIdx.x; w < a.items; w += gridDim.x) {
+        const int64_t line = w / a.bpl, b = w - line * a.bpl;
+        int64_t in_off, out_off;
+        group_line_off(a, line, in_off, out_off);
+        const T *base = in + in_off;
+        const int64_t k0 = b * a.span;
+        const int64_t k1 = k0 + a.span < a.K ? k0 + a.span : a.K;
+        A acc[NG];
+#pragma unroll
+        for (int g = 0; g < NG; ++g) acc[g] = R::Acc::identity();
+
+        // whole units of [k0, k1); span is a multiple of 256 x 16 bytes
+#pragma unroll 2
+        for (int64_t u = k0 / V + tid; u < k1 / V; u += GROUP_BLOCK) {
+            const L unit = *reinterpret_cast<const L *>(base + u * V * a.sK);
+            T e[V];
+            uint8_t l[V];
+            __builtin_memcpy(e, &unit, sizeof(L));
+            __builtin_memcpy(l, __builtin_assume_aligned(lab + u * V, V), V);
+#pragma unroll
+            for (int i = 0; i < V; ++i)
+                group_select_add<T, OP>(acc, e[i], l[i], a.skipna);
+        }
+        if (VEC && k1 == a.K) {         // the rows past the line's last unit
+            const int64_t k = a.K / V * V + tid;
+            if (k >= k0 && k < a.K)
+                group_select_add<T, OP>(acc, base[k * a.sK], lab[k],
+                                        a.skipna);
+        }
+
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+            if (g < a.ngroups) {
+                const A v = group_wave_tree<typename R::Acc, A>(acc[g]);
+                if ((tid & 63) == 0) wave_acc[tid >> 6][g] = v;
+            }
+        }
+        __syncthreads();
+        if (tid < a.ngroups) {
+            A v = wave_acc[0][tid];
+#pragma unroll
+            for (int q = 1; q < GROUP_BLOCK / 64; ++q)
+                v = R::Acc::comb(v, wave_acc[q][tid]);
+            part[w * a.ngroups + tid] = v;
+        }
+        __syncthreads();
+    }
+}
+
+template <typename T, int OP>
+__global__ __launch_bounds__(256) GEMM_NO_PK_F32 void group_gather_kernel(
+    const T *__restrict__ in, GroupArgs a,
+    const int32_t *__restrict__ members, const int32_t *__restrict__ seg,
+    typename GroupRed<T, OP>::A *__restrict__ part) {
+    using R = GroupRed<T, OP>;
+    using A = typename R::A;
+    const int lane = threadIdx.x & 63;
+    constexpr int WAVES = GROUP_BLOCK / 64;
+    for (int64_t w = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
+         w < a.items; w += (int64_t)gridDim.x * WAVES) {
+        const int64_t line = w / a.nslots, s = w - line * a.nslots;
+        int64_t g, m0, m1;
+        if (!group_slot(seg, a.ngroups, a.K, GROUP_GATHER_CHUNK, s, g, m0,
+                        m1))
+            continue;                           // the whole wave
+        int64_t in_off, out_off;
+        group_line_off(a, line, in_off, out_off);
+        const T *base = in + in_off;
+        A acc = R::Acc::identity();
+#pragma unroll 4
+        for (int64_t j = m0 + lane; j < m1; j += 64)
+            acc = R::Acc::comb(
+                acc, R::lift(base[group_member(members, j, a.K) * a.sK],
+                             a.skipna));
+        acc = group_wave_tree<typename R::Acc, A>(acc);
+        if (lane == 0) part[w] = acc;
+    }
+}
+
+// the second launch of ROWS_SPLIT, LINE_SELECT and LINE_GATHER: one thread
+// per output combines its partials in ascending order
+template <typename A, int OP>
+__global__ __launch_bounds__(256) GEMM_NO_PK_F32 void group_finish_kernel(
+    const A *__restrict__ part, GroupArgs a, GroupFinArgs f,
+    const int32_t *__restrict__ seg, A *__restrict__ out) {
+    using Acc = GroupAcc<A, OP>;
+    const int64_t n = a.ngroups * a.P;
+    const int64_t S = (int64_t)gridDim.x * GROUP_BLOCK;
+    for (int64_t e = (int64_t)blockIdx.x * GROUP_BLOCK + threadIdx.x; e < n;
+         e += S) {
+        const int64_t g = e / a.P, p = e - g * a.P;
+        int64_t base = 0, count = f.count;
+        if (f.chunk) {
+            const int64_t s0 = group_seg(seg, g, a.K);
+            const int64_t s1 = group_seg(seg, g + 1, a.K);
+            base = s0 / f.chunk + g;
+            count = s1 > s0 ? (s1 - s0 + f.chunk - 1) / f.chunk : 0;
+        }
+        const A *src = part + base * f.slot_stride + p * f.p_stride
+                       + g * f.g_stride;
+        A acc = Acc::identity();
+        for (int64_t c = 0; c < count; ++c)
+            acc = Acc::comb(acc, src[c * f.slot_stride]);
+        int64_t in_off, out_off;
+        group_line_off(a, p, in_off, out_off);
+        out[g * a.osG + out_off] = acc;
+    }
+}
+
+// rt_dtype of the accumulator (and of `out`) for an input dtype and op
+int group_acc_dtype(int dtype, int op) {
+    if (op == GROUP_COUNT_VALID) return RT_I64;
+    if (op == GROUP_MIN || op == GROUP_MAX) return dtype;
+    return dtype == RT_F64 || dtype == RT_F32 ? dtype : RT_I64;
+}
+
+struct GroupPlan {
+    int regime;
+    GroupArgs a;
+    bool vec_ok;             // strides and extents allow 16-byte loads
+    int64_t part_bytes;      // partials at the start of the scratch
+    int64_t scratch_bytes;   // partials, then LINE_SELECT's label bytes
+};
+
+int64_t group_abs(int64_t v) { return v < 0 ? -v : v; }
+int64_t group_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// Regime, axis roles and launch geometry from the shape and strides alone
+// (no pointer, no label): what rt_group_regime and rt_group_scratch report
+// is what rt_group_reduce runs.  Arguments are validated by the callers.
+void group_plan(int nd, const int64_t *shape, const int64_t *strides,
+                const int64_t *out_strides, int axis, int dtype, int op,
+                int64_t ngroups, GroupPlan *plan) {
+    GroupArgs &a = plan->a;
+    const int es = dtype_size(dtype);
+    const int64_t V = 16 / es;
+    a.K = shape[axis];
+    a.sK = strides[axis];
+    a.osG = out_strides ? out_strides[axis] : 0;
+    a.ngroups = ngroups;
+    a.nslots = a.nu = a.tiles_in = a.tiles = a.bpl = a.span = 0;
+    a.lpr_shift = a.split = a.skipna = 0;
+
+    // the lane axis of ROWS: the last other axis of unit stride; the group
+    // axis takes the lanes (LINE_*) when it alone has the unit stride, or
+    // when there is no other axis to take them
+    int lane = -1, others = 0, fallback = -1;
+    for (int d = 0; d < nd; ++d) {
+        if (d == axis || shape[d] == 1) continue;
+        ++others;
+        if (group_abs(strides[d]) == 1) lane = d;
+        if (strides[d] != 0
+            && (fallback < 0 || group_abs(strides[d])
+                                    <= group_abs(strides[fallback])))
+            fallback = d;
+    }
+    bool line = others == 0;
+    if (!line && lane < 0) {
+        if (group_abs(a.sK) == 1)
+            line = true;
+        else
+            lane = fallback;
+    }
+    if (!line && lane < 0)      // every other axis is a broadcast
+        for (int d = 0; d < nd; ++d)
+            if (d != axis && shape[d] != 1) lane = d;
+
+    // the other axes, right-aligned, the lane axis last
+    for (int d = 0; d < 3; ++d) {
+        a.ext[d] = 1;
+        a.str[d] = a.ostr[d] = 0;
+    }
+    int k = 2;
+    auto place = [&](int d) {
+        a.ext[k] = shape[d];
+        a.str[k] = strides[d];
+        a.ostr[k] = out_strides ? out_strides[d] : 0;
+        --k;
+    };
+    if (!line) place(lane);
+    for (int d = nd - 1; d >= 0; --d)
+        if (d != axis && (line || d != lane)) place(d);
+    if (!line) {
+        // fold an axis that is dense over the lane axis, in and out, into it
+        while (a.ext[1] > 1 && a.str[1] == a.ext[2] * a.str[2]
+               && a.ostr[1] == a.ext[2] * a.ostr[2]) {
+            a.ext[2] *= a.ext[1];
+            a.ext[1] = a.ext[0];
+            a.str[1] = a.str[0];
+            a.ostr[1] = a.ostr[0];
+            a.ext[0] = 1;
+            a.str[0] = a.ostr[0] = 0;
+        }
+    }
+    a.P = a.ext[0] * a.ext[1] * a.ext[2];
+    const int64_t asz = dtype_size(group_acc_dtype(dtype, op));
+
+    plan->part_bytes = 0;
+    int64_t label_bytes = 0;
+    if (!line) {
+        plan->vec_ok = a.str[2] == 1 && a.ext[2] % V == 0 && a.sK % V == 0
+                       && a.str[0] % V == 0 && a.str[1] % V == 0;
+        a.split = ngroups * group_cdiv(a.P, GROUP_BLOCK) < GROUP_SPLIT_BLOCKS
+                  && a.K >= 2 * GROUP_CHUNK + 1;
+        plan->regime = a.split ? GROUP_ROWS_SPLIT : GROUP_ROWS;
+        if (a.split) {
+            a.nslots = a.K / GROUP_CHUNK + ngroups;
+            plan->part_bytes = a.nslots * a.P * asz;
+        }
+    } else if (ngroups <= GROUP_SELECT_MAX) {
+        plan->regime = GROUP_LINE_SELECT;
+        plan->vec_ok = a.sK == 1 && a.K >= V && a.str[0] % V == 0
+                       && a.str[1] % V == 0 && a.str[2] % V == 0;
+        const int64_t tile = GROUP_BLOCK * V;
+        int64_t bpl = GROUP_SELECT_BLOCKS / a.P;
+        if (bpl < 1) bpl = 1;
+        if (bpl > group_cdiv(a.K, tile)) bpl = group_cdiv(a.K, tile);
+        a.span = group_cdiv(group_cdiv(a.K, bpl), tile) * tile;
+        a.bpl = group_cdiv(a.K, a.span);
+        a.items = a.P * a.bpl;
+        plan->part_bytes = (a.items * ngroups * asz + 15) & ~(int64_t)15;
+        label_bytes = a.K;
+    } else {
+        plan->regime = GROUP_LINE_GATHER;
+        plan->vec_ok = false;
+        a.nslots = a.K / GROUP_GATHER_CHUNK + ngroups;
+        a.items = a.P * a.nslots;
+        plan->part_bytes = a.items * asz;
+    }
+    plan->scratch_bytes = plan->part_bytes + label_bytes;
+}
+
+// ROWS launch geometry, once the load width is known
+void group_rows_geometry(GroupArgs *a, int64_t V) {
+    a->nu = a->ext[2] / V;
+    int s = 0;
+    while (s < 8 && (1LL << s) < a->nu) ++s;
+    a->lpr_shift = s;
+    a->tiles_in = group_cdiv(a->nu, 1LL << s);
+    a->tiles = a->tiles_in * group_cdiv(a->ext[0] * a->ext[1], 256 >> s);
+    a->items = (a->split ? a->nslots : a->ngroups) * a->tiles;
+}
+
+unsigned group_grid(int64_t blocks) {
+    return (unsigned)(blocks < 1 ? 1
+                      : blocks > GROUP_GRID_CAP ? GROUP_GRID_CAP : blocks);
+}
+
+template <typename A>
+int group_finish(hipStream_t st, int aop, const void *part,
+                 const GroupArgs &a, const GroupFinArgs &f, const void *seg,
+                 void *out) {
+    const unsigned grid =
+        group_grid(group_cdiv(a.ngroups * a.P, GROUP_BLOCK));
+#define GROUP_FIN(OP)                                                      \
+    hipLaunchKernelGGL((group_finish_kernel<A, OP>), dim3(grid),           \
+                       dim3(GROUP_BLOCK), 0, st,                           \
+                       static_cast<const A *>(part), a, f,                 \
+                       static_cast<const int32_t *>(seg),                  \
+                       static_cast<A *>(out))
+    if constexpr (std::is_floating_point<A>::value
+                  || std::is_same<A, int64_t>::value) {
+        if (aop == GROUP_SUM) GROUP_FIN(GROUP_SUM);
+        if (aop == GROUP_PROD) GROUP_FIN(GROUP_PROD);
+    }
+    if (aop == GROUP_MIN) GROUP_FIN(GROUP_MIN);
+    if (aop == GROUP_MAX) GROUP_FIN(GROUP_MAX);
+#undef GROUP_FIN
+    return launched("rt_group_reduce (combine)");
+}
+
+template <typename T, int OP>
+int group_run(hipStream_t st, const T *src, bool aligned, GroupPlan &plan,
+              const int32_t *members, const int32_t *seg, void *out,
+              void *scratch) {
+    using R = GroupRed<T, OP>;
+    using A = typename R::A;
+    GroupArgs &a = plan.a;
+    A *part = static_cast<A *>(scratch);
+    A *outp = static_cast<A *>(out);
+    const bool vec = plan.vec_ok && aligned;
+    GroupFinArgs f = {0, 0, 0, 0, 0};
+
+    if (plan.regime <= GROUP_ROWS_SPLIT) {
+        group_rows_geometry(&a, vec ? 16 / (int64_t)sizeof(T) : 1);
+        const unsigned grid = group_grid(a.items);
+        if (vec)
+            hipLaunchKernelGGL((group_rows_kernel<T, OP, true>), dim3(grid),
+                               dim3(GROUP_BLOCK), 0, st, src, a, members,
+                               seg, outp, part);
+        else
+            hipLaunchKernelGGL((group_rows_kernel<T, OP, false>), dim3(grid),
+                               dim3(GROUP_BLOCK), 0, st, src, a, members,
+                               seg, outp, part);
+        if (launched("rt_group_reduce (rows)")) return 1;
+        if (!a.split) return 0;
+        f.chunk = GROUP_CHUNK;
+        f.slot_stride = a.P;
+        f.p_stride = 1;
+    } else if (plan.regime == GROUP_LINE_SELECT) {
+        uint8_t *lab = static_cast<uint8_t *>(scratch) + plan.part_bytes;
+        hipLaunchKernelGGL(group_labels_kernel,
+                           dim3(group_grid(group_cdiv(a.K, GROUP_BLOCK))),
+                           dim3(GROUP_BLOCK), 0, st, members, seg, a.K,
+                           (int)a.ngroups, lab);
+        if (launched("rt_group_reduce (labels)")) return 1;
+        const unsigned grid = group_grid(a.items);
+        if (vec)
+            hipLaunchKernelGGL((group_select_kernel<T, OP, true>),
+                               dim3(grid), dim3(GROUP_BLOCK), 0, st, src, a,
+                               lab, part);
+        else
+            hipLaunchKernelGGL((group_select_kernel<T, OP, false>),
+                               dim3(grid), dim3(GROUP_BLOCK), 0, st, src, a,
+                               lab, part);
+        if (launched("rt_group_reduce (select)")) return 1;
+        f.count = a.bpl;
+        f.slot_stride = a.ngroups;
+        f.p_stride = a.bpl * a.ngroups;
+        f.g_stride = 1;
+    } else {
+        hipLaunchKernelGGL((group_gather_kernel<T, OP>),
+                           dim3(group_grid(group_cdiv(a.items, 4))),
+                           dim3(GROUP_BLOCK), 0, st, src, a, members, seg,
+                           part);
+        if (launched("rt_group_reduce (gather)")) return 1;
+        f.chunk = GROUP_GATHER_CHUNK;
+        f.slot_stride = 1;
+        f.p_stride = a.nslots;
+    }
+    return group_finish<A>(st, R::AOP, part, a, f, seg, out);
+}
+
+// the checks shared by the four entry points; *n_out = elements of the box
+int group_validate(const char *who, int nd, const int64_t *shape,
+                   const int64_t *strides, const int64_t *out_strides,
+                   int axis, int dtype, int op, int64_t ngroups,
+                   int64_t *n_out) {
+    if (box_extents(who, nd, 1, shape, strides, out_strides, n_out)) return 1;
+    if (axis < 0 || axis >= nd) return fail(who, "axis out of range");
+    if (dtype < RT_F64 || dtype > RT_U8) return fail(who, "bad dtype");
+    if (op < GROUP_SUM || op > GROUP_COUNT_VALID) return fail(who, "bad op");
+    if (ngroups < 1) return fail(who, "ngroups < 1");
+    if (ngroups >= (1LL << 31)) return fail(who, "ngroups out of range");
+    if (shape[axis] >= (1LL << 31))
+        return fail(who, "group axis too long for int32 members");
+    if (shape[axis] && *n_out / shape[axis] > (1LL << 46) / ngroups)
+        return fail(who, "result too large (ngroups x other extents)");
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int rt_group_geometry(int *block, int *member_tile, int *chunk,
+                                 int *split_blocks, int *select_max,
+                                 int *select_blocks, int *gather_chunk,
+                                 int *grid_cap) {
+    if (block) *block = GROUP_BLOCK;
+    if (member_tile) *member_tile = GROUP_MEMBER_TILE;
+    if (chunk) *chunk = GROUP_CHUNK;
+    if (split_blocks) *split_blocks = GROUP_SPLIT_BLOCKS;
+    if (select_max) *select_max = GROUP_SELECT_MAX;
+    if (select_blocks) *select_blocks = GROUP_SELECT_BLOCKS;
+    if (gather_chunk) *gather_chunk = GROUP_GATHER_CHUNK;
+    if (grid_cap) *grid_cap = GROUP_GRID_CAP;
+    return 0;
+}
+
+extern "C" int rt_group_regime(int nd, const int64_t *shape,
+                               const int64_t *strides, int axis, int dtype,
+                               int64_t ngroups) {
+    int64_t n;
+    if (group_validate("rt_group_regime", nd, shape, strides, strides, axis,
+                       dtype, GROUP_SUM, ngroups, &n))
+        return -1;
+    GroupPlan plan;
+    group_plan(nd, shape, strides, nullptr, axis, dtype, GROUP_SUM, ngroups,
+               &plan);
+    return plan.regime;
+}
+
+extern "C" int64_t rt_group_scratch(int nd, const int64_t *shape,
+                                    const int64_t *strides, int axis,
+                                    int dtype, int op, int64_t ngroups) {
+    int64_t n;
+    if (group_validate("rt_group_scratch", nd, shape, strides, strides, axis,
+                       dtype, op, ngroups, &n))
+        return -1;
+    if (n == 0) return 0;
+    GroupPlan plan;
+    group_plan(nd, shape, strides, nullptr, axis, dtype, op, ngroups, &plan);
+    return plan.scratch_bytes;
+}
+
+extern "C" int rt_group_reduce(uintptr_t stream, const void *in,
+                               int64_t in_off, int nd, const int64_t *shape,
+                               const int64_t *strides, int axis, int dtype,
+                               int op, int skipna, const void *members,
+                               const void *seg, int64_t ngroups, void *out,
+                               const int64_t *out_strides, void *scratch) {
+    const char *who = "rt_group_reduce";
+    int64_t n;
+    if (group_validate(who, nd, shape, strides, out_strides, axis, dtype, op,
+                       ngroups, &n))
+        return 1;
+    if (n == 0) return 0;
+    if (!in) return fail(who, "NULL in");
+    if (!members) return fail(who, "NULL members");
+    if (!seg) return fail(who, "NULL seg");
+    if (!out) return fail(who, "NULL out");
+    GroupPlan plan;
+    group_plan(nd, shape, strides, out_strides, axis, dtype, op, ngroups,
+               &plan);
+    plan.a.skipna = skipna != 0;
+    if (plan.scratch_bytes && !scratch) return fail(who, "NULL scratch");
+    if (reinterpret_cast<uintptr_t>(scratch) & 15)
+        return fail(who, "scratch not 16-byte aligned");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int32_t *mem = static_cast<const int32_t *>(members);
+    const int32_t *sg = static_cast<const int32_t *>(seg);
+
+    return dtype_dispatch<7>(who, dtype, [&](auto t) {
+        using T = decltype(t);
+        const T *src = static_cast<const T *>(in) + in_off;
+        const bool aligned = reinterpret_cast<uintptr_t>(src) % 16 == 0;
+        switch (op) {
+            case GROUP_SUM:
+                return group_run<T, GROUP_SUM>(st, src, aligned, plan, mem,
+                                               sg, out, scratch);
+            case GROUP_PROD:
+                return group_run<T, GROUP_PROD>(st, src, aligned, plan, mem,
+                                                sg, out, scratch);
+            case GROUP_MIN:
+                return group_run<T, GROUP_MIN>(st, src, aligned, plan, mem,
+                                               sg, out, scratch);
+            case GROUP_MAX:
+                return group_run<T, GROUP_MAX>(st, src, aligned, plan, mem,
+                                               sg, out, scratch);
+        }
+        return group_run<T, GROUP_COUNT_VALID>(st, src, aligned, plan, mem,
+                                               sg, out, scratch);
+    });
 }

@@ -125,6 +125,11 @@ _RT_ABI = {
                             _p64]),
     "rt_partition_scratch": (_i64, [_i64, _int]),
     "rt_partition_geometry": (_int, [ctypes.POINTER(_int)] * 4),
+    "rt_group_reduce": (_int, [_sz, _vp, _i64, _int, _p64, _p64, _int, _int,
+                               _int, _int, _vp, _vp, _i64, _vp, _p64, _vp]),
+    "rt_group_scratch": (_i64, [_int, _p64, _p64, _int, _int, _int, _i64]),
+    "rt_group_regime": (_int, [_int, _p64, _p64, _int, _int, _i64]),
+    "rt_group_geometry": (_int, [ctypes.POINTER(_int)] * 8),
     "rt_stream_sync": (_int, [_sz]),
     "rt_device_sync": (_int, []),
     "rt_event_create": (_int, [_pvp]),
@@ -221,6 +226,15 @@ def partition_geometry(lib):
                    (v.value for v in vals)))
     geo["tile"] = geo["block"] * geo["keys_per_lane"]
     return geo
+
+
+def group_geometry(lib):
+    """rt_group_geometry as a dict (host arithmetic; needs no GPU)."""
+    vals = [ctypes.c_int() for _ in range(8)]
+    lib.rt_group_geometry(*[ctypes.byref(v) for v in vals])
+    return dict(zip(("block", "member_tile", "chunk", "split_blocks",
+                     "select_max", "select_blocks", "gather_chunk",
+                     "grid_cap"), (v.value for v in vals)))
 
 
 def _hb_arg_chunks(nd, axis, nout, K):
@@ -1270,6 +1284,49 @@ class HipBackend:
             edt, int(nbins), ctypes.c_void_p(counts.data_ptr()),
             ctypes.c_void_p(bad.data_ptr())), "rt_hist")
         return counts, bad
+
+    # -- groupby reductions (runtime.group_op) --------------------------------
+    #
+    # The hook of ramba_amd/groupby.py on rt_group_reduce.  The operand is
+    # read in place through the view's strides; the CSR is uploaded as int32
+    # and the partial stays on the device.
+
+    def group_geometry(self):
+        """The compiled-in constants of rt_group_reduce, by name."""
+        return group_geometry(self.lib)
+
+    def group_partial(self, bd, rt, view, lb, dim, members, seg, ngroups, op,
+                      skipna):
+        from .groupby import acc_dtype
+        d_, _, cstrides, pads = rt.shard_geometry(bd)
+        off0, strides = view.operand_addressing(lb[0], cstrides, d_[0], pads)
+        shape = box_shape(lb)
+        nd = len(shape)
+        dtc = RT_DTYPE[str(np.dtype(bd.dtype))]
+        out = self.torch.empty(
+            tuple(ngroups if d == dim else s for d, s in enumerate(shape)),
+            dtype=self._tdt(acc_dtype(bd.dtype, op)), device="cuda")
+        nbytes = self.lib.rt_group_scratch(
+            nd, _i64arr(shape), _i64arr(strides), int(dim), dtc, int(op),
+            int(ngroups))
+        if nbytes < 0:
+            self._check(1, "rt_group_scratch")
+        scratch = self.torch.empty(nbytes, dtype=self.torch.uint8,
+                                   device="cuda") if nbytes else None
+        # (a CSR that is already on the device is taken as it is)
+        dev_members, dev_seg = (
+            t if isinstance(t, self.torch.Tensor)
+            else self.torch.from_numpy(t).to("cuda") for t in (members, seg))
+        self._check(self.lib.rt_group_reduce(
+            self._stream(), ctypes.c_void_p(self._cont(bd).data_ptr()),
+            int(off0), nd, _i64arr(shape), _i64arr(strides), int(dim), dtc,
+            int(op), int(bool(skipna)),
+            ctypes.c_void_p(dev_members.data_ptr()),
+            ctypes.c_void_p(dev_seg.data_ptr()), int(ngroups),
+            ctypes.c_void_p(out.data_ptr()), _i64arr(out.stride()),
+            ctypes.c_void_p(scratch.data_ptr()) if nbytes else None),
+            "rt_group_reduce")
+        return out
 
     # -- median / percentile / quantile (runtime.select_op) -------------------
     #

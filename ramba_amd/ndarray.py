@@ -17,6 +17,7 @@ from . import deferred, ir
 from . import histogram as _hg   # the submodule; the package's `histogram` is the function below
 from .common import (contiguous_divisions, default_border,
                      default_divisions)
+from .groupby import Groupby
 from .shardview import View, exec_boxes, spans_trailing_axes
 
 
@@ -722,6 +723,11 @@ class ndarray:
 
     def take(self, indices, axis=None, out=None, mode="raise"):
         return take(self, indices, axis=axis, out=out, mode=mode)
+
+    def groupby(self, dim, value_to_group, num_groups=None):
+        """The reference's ndarray.groupby (ramba.py:6896): a `Groupby` of
+        the rows of axis `dim` by their integer labels (groupby.py)."""
+        return Groupby(self, dim, value_to_group, num_groups)
 
     def rollaxis(self, axis, start=0):
         n = self.ndim

@@ -1480,6 +1480,77 @@ Runtime.hist_op = hist_op
 
 
 # ---------------------------------------------------------------------------
+# groupby reductions (the reference's RambaGroupby, ramba.py:10290-10607).  A
+# keyed reduction of values: every rank reduces the exec box of the view
+# that it owns, the labels of the box's rows as a CSR, into a partial shaped
+# like the box with ngroups rows on `dim` (the group_partial hook, ramba_amd/
+# groupby.py).  The result has default divisions and starts as the identity;
+# each owner receives the pieces of the partials that cover its core and
+# merges them (rt_combine_box on HIP) in ASCENDING SOURCE-RANK ORDER, its own
+# piece in its place.  A float result therefore does not depend on the order
+# of arrival, also when the array is split along `dim`.
+# ---------------------------------------------------------------------------
+
+def group_op(self, arr, dim, labels, ngroups, op, skipna):
+    """The reduction `op` of ramba_amd/groupby.py over the rows of `dim`
+    grouped by the host int64 `labels`, as a bdarray."""
+    from . import groupby as _gb
+    bd, v = arr.bdarray, arr.view
+    hooks = _gb.hooks_for(self.backend)
+    out_shape = tuple(ngroups if d == dim else s
+                      for d, s in enumerate(v.shape))
+    wire = _gb.acc_dtype(bd.dtype, op)      # bool travels as uint8
+    out_bd = self.new_result(out_shape, _gb.result_dtype(bd.dtype, op),
+                             default_divisions(self.world, out_shape))
+    self.backend.fill_container(out_bd, self, _gb.identity(bd.dtype, op))
+
+    lbs = exec_boxes(v, bd.divisions)
+    lb = lbs[self.rank]
+    part = None
+    if lb is not None:
+        members, seg = _gb.build_csr(
+            labels[int(lb[0, dim]):int(lb[1, dim]) + 1], ngroups)
+        part = hooks.group_partial(bd, self, v, lb, dim, members, seg,
+                                   ngroups, op, skipna)
+
+    def covered(box):       # the result cells a rank's partial covers
+        pb = box.copy()
+        pb[0, dim], pb[1, dim] = 0, ngroups - 1
+        return pb
+
+    cores = [self.core_box(out_bd, s) for s in range(self.world)]
+    sends, recvs, merges = [], [], []
+    for src in range(self.world):           # ascending: the merge order
+        if lbs[src] is None:
+            continue
+        pb = covered(lbs[src])
+        for dst, core in enumerate(cores):
+            bx = box_intersect(pb, core)
+            if bx is None:
+                continue
+            if src == self.rank:
+                piece = part[box_slices(bx, pb[0])].contiguous()
+                if dst == self.rank:
+                    merges.append((bx, piece))
+                else:
+                    sends.append((dst, piece))
+            elif dst == self.rank:
+                buf = self.backend.new_message_buffer(box_shape(bx), wire)
+                recvs.append((src, buf))
+                merges.append((bx, buf))
+    if sends or recvs:
+        self.backend.exchange(sends, recvs)
+    for (bx, buf) in merges:
+        self.backend.combine_box_into_container(out_bd, self, bx, buf,
+                                                _gb.COMBINE[op])
+    self.backend.free_temps()
+    return out_bd
+
+
+Runtime.group_op = group_op
+
+
+# ---------------------------------------------------------------------------
 # sort / argsort (numpy.sort, numpy.argsort, always the stable result; the
 # reference has neither).  The frontend hands over a constructed array on
 # contiguous (axis-0) divisions, sorted along its LAST axis through the hooks
