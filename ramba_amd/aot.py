@@ -74,6 +74,14 @@ class AotCompileBackend:
             fams = codegen.find_stencil_families(plan)
             if fams:
                 self._cc(codegen.generate_load_tiled(plan, fams).source)
+        # and the plane-marching variant of a 3-D plan
+        if (len(plan.itershape) == 3
+                and int(np.prod(plan.itershape)) >= int(os.environ.get(
+                    "RAMBA_LT3_MIN", str(codegen.LT3_MIN)))):
+            fams = codegen.find_stencil_families_3d(plan)
+            gk3 = codegen.generate_load_tiled_3d(plan, fams) if fams else None
+            if gk3 is not None:
+                self._cc(gk3.source)
         return [ir.reduction_identity(s.kind, s.dtype)
                 for s in plan.reductions]
 
@@ -191,6 +199,23 @@ def seed(fuzz_seeds=None):
         ra.sync()
         del X2, Y2
         ra.sync()
+    # 7-point 3-D updates, fp32 and fp64, at two geometry classes of the
+    # plane-marching kernel (SEG0 keys on the iteration shape)
+    for dt in (np.float32, np.float64):
+        for SS in (128, 512):
+            X3 = ra.zeros((SS + 2, SS + 2, SS + 2), dtype=dt)
+            Y3 = ra.zeros((SS + 2, SS + 2, SS + 2), dtype=dt)
+            ra.sync()
+            # user data, not a fill: at 512^3 a fill would be recomputed
+            # from the index (common.remat) and leave no family to stage
+            X3.bdarray.pure = None
+            Y3[1:-1, 1:-1, 1:-1] = 0.5 * X3[1:-1, 1:-1, 1:-1] + 0.25 * (
+                X3[:-2, 1:-1, 1:-1] + X3[2:, 1:-1, 1:-1]
+                + X3[1:-1, :-2, 1:-1] + X3[1:-1, 2:, 1:-1]
+                + X3[1:-1, 1:-1, :-2] + X3[1:-1, 1:-1, 2:])
+            ra.sync()
+            del X3, Y3
+            ra.sync()
     # configs[4] mixed fp64 (Z materialised first so the pair takes the
     # staged/tiled path, like the bench loop's steady state)
     Z = ra.zeros((64, 64), dtype=np.float64)

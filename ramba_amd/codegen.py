@@ -644,12 +644,13 @@ class KernelArgs:
         else:
             self.i64(name, ("scalar_i", name))
 
-    def view(self, ct, name, bounds=False):
+    def view(self, ct, name, bounds=False, nd=2):
         """A 2-D view: pointer, element offset, two strides and, with
-        `bounds`, the inclusive box [lo0, hi0] x [lo1, hi1]."""
+        `bounds`, the inclusive box [lo0, hi0] x [lo1, hi1].  `nd=3` gives
+        three strides."""
         self.ptr(ct, f"{name}_ptr")
-        for f in ("off", "s0", "s1") + (("lo0", "hi0", "lo1", "hi1")
-                                        if bounds else ()):
+        for f in ("off",) + tuple(f"s{d}" for d in range(nd)) + (
+                ("lo0", "hi0", "lo1", "hi1") if bounds else ()):
             self.i64(f"{name}_{f}")
 
     def decl(self):
@@ -677,7 +678,7 @@ class KernelArgs:
 class GeneratedKernel:
     """One generated kernel: source, entry name and argument struct, plus
     whatever its launch needs.  `kind` selects the backend's launch path:
-    'fused', 'finish', 'axred', 'tiled' or 'lt'."""
+    'fused', 'finish', 'axred', 'tiled', 'lt' or 'lt3'."""
 
     def __init__(self, kind, key, source, kname, args, vec=1, nd=0, nred=0,
                  anchor=None, yblock=1, finish=None, lane_split=False,
@@ -696,7 +697,7 @@ class GeneratedKernel:
         self.finish = finish         # fused reductions: the finish kernel
         self.lane_split = lane_split
         self.tile = tile             # load-tiled: (TH, CW, SEG)
-        self.fam_meta = fam_meta     # load-tiled: [(rep, anchor, s0)]
+        self.fam_meta = fam_meta     # load-tiled: [(rep, anchor, s0[, s1])]
         self.others = others         # load-tiled: non-family operand names
 
     @property
@@ -1942,4 +1943,317 @@ def generate_load_tiled(plan, fams):
     return GeneratedKernel(
         "lt", key, "\n".join(L), kname, A, tile=(TH, CW, SEG),
         fam_meta=[(rep, anchor, s0) for (anchor, s0, dt, mem, rep) in fams],
+        others=[o.name for o in other_ops])
+
+
+# ---------------------------------------------------------------------------
+# 3-D load-tiled stencil kernel: 2.5-D plane marching.  A workgroup owns a
+# (column strip, row tile, plane segment) and walks its segment one output
+# plane at a time; the E0+1 input planes an output plane needs live in an
+# LDS ring, so each step loads ONE new plane over the oldest.  The generic
+# kernel gives a 3-D plan one block per row, so every +-1 neighbour along
+# axes 0 and 1 is its own trip to L2 (7 loads per output for a 7-point
+# update); here a family costs (1 + E1/TH1)(1 + E2/CW)(1 + E0/SEG0) loads.
+# ---------------------------------------------------------------------------
+
+LT3_MAXD = 4                  # stencil radius served per axis
+LT3_MAXE = 2 * LT3_MAXD       # so a family's box extends <= 8 per axis
+LT3_LDS_HARD = 64 * 1024      # static __shared__ limit
+# tile rows: at 512^3 a 7-point update takes 0.36 / 0.52 ms (fp32 / fp64)
+# with 4 rows, 0.44 / 0.53 with 8 and 0.63 / 0.74 with 16 -- 19 KB of LDS
+# and 8 workgroups per CU beat the smaller halo
+# (profiles/stencil3d_sweep.jsonl)
+LT3_TH = 4
+LT3_WORK_MIN = 1024           # work items wanted: 4 per CU on 256 CUs
+# default RAMBA_LT3_MIN, elements per plan: 128^3, the smallest size measured
+# (kernel alone 27 vs 40 us; profiles/stencil3d_bench.jsonl)
+LT3_MIN = 1 << 21
+
+
+def find_stencil_families_3d(plan):
+    """The 3-D analogue of find_stencil_families: groups of >= 3 unwritten
+    container operands on one buffer with strides (s0, s1, 1), s0 >= s1 > 0,
+    whose offsets differ by d0*s0 + d1*s1 + d2 inside a box of extent
+    <= LT3_MAXE per axis.  Returns [(anchor_off, s0, s1, dtype,
+    [(name, d0, d1, d2)], rep)] with every delta >= 0 from the anchor (the
+    box's low corner), or None if the plan does not qualify."""
+    if len(plan.itershape) != 3 or plan.reductions:
+        return None
+    E = LT3_MAXE
+    written = {st.target for st in plan.statements}
+    groups = {}
+    for op in plan.operands:
+        if op.kind != "container" or op.name in written:
+            continue
+        st = tuple(op.strides)
+        # s1 > 2E keeps a column delta from reading as a row delta
+        if len(st) != 3 or st[2] != 1 or not (st[0] >= st[1] > 2 * E):
+            continue
+        groups.setdefault((id(op.bd), st), []).append(op)
+    fams = []
+    for ((_, (s0, s1, _)), ops) in groups.items():
+        if len(ops) < 3:
+            continue
+        base = min(o.offset0 for o in ops)
+        # deltas from the lowest member: d0 >= 0, d1 and d2 of either sign
+        # (a star's lowest member is its axis-0 arm, not the box corner);
+        # shifting by (E, E) makes the floor decomposition exact
+        mem = []
+        for o in ops:
+            d0, rem = divmod(o.offset0 - base + E * s1 + E, s0)
+            d1, d2 = divmod(rem, s1)
+            if d0 > E or d1 > 2 * E or d2 > 2 * E:
+                mem = None
+                break
+            mem.append((o.name, d0, d1 - E, d2 - E))
+        if not mem:
+            continue
+        m1 = min(m[2] for m in mem)
+        m2 = min(m[3] for m in mem)
+        mem = [(n, d0, d1 - m1, d2 - m2) for (n, d0, d1, d2) in mem]
+        ext = [max(m[k] for m in mem) for k in (1, 2, 3)]
+        # s0 >= s1 * (E1 + 1): the decomposition is the container's own, so
+        # the tile footprint is the bounding box of the members' views
+        if max(ext) > E or s0 < s1 * (ext[1] + 1):
+            continue
+        fams.append((base + m1 * s1 + m2, s0, s1, str(ops[0].dtype), mem,
+                     ops[0].name))
+    return fams or None
+
+
+_LT3_VEC = {("double", 2): "d2_t", ("float", 4): "f4_t", ("float", 2): "f2_t",
+            ("long long", 2): "l2_t", ("int", 4): "i4_t", ("int", 2): "i2_t",
+            ("short", 4): "s4_t", ("short", 2): "s2_t",
+            ("signed char", 4): "c4_t", ("signed char", 2): "c2_t",
+            ("unsigned char", 4): "b4_t", ("unsigned char", 2): "b2_t"}
+
+
+def _lt3_geometry(itershape, fam_ext, fam_items, V):
+    """(TH1, NCH, SEG0, LDS bytes) for an iteration shape, or None when no
+    tile fits the static LDS limit.
+
+    TH1 = LT3_TH and NCH = 64 (a row of a strip is 1 KB of 16-byte units);
+    strips narrow to 32 and 16 units only when the rings overflow the static
+    LDS limit (a radius-4 star's 9-plane ring).  SEG0 starts at 4*E0 (overlap
+    planes re-read <= 1.25x) and doubles up to 64 while the grid keeps
+    LT3_WORK_MIN work items.  RAMBA_LT3_TH / _NCH / _SEG pin any of the
+    three."""
+    n0, n1, n2 = itershape
+    env = os.environ.get
+    TH1 = int(env("RAMBA_LT3_TH", str(LT3_TH)))
+    nchs = [int(env("RAMBA_LT3_NCH"))] if env("RAMBA_LT3_NCH") \
+        else [64, 32, 16]
+
+    def lds_bytes(th, nch):
+        tot = 0
+        for (e0, e1, e2), item in zip(fam_ext, fam_items):
+            pitch = -(-(nch * V + e2) // V) * V + V
+            tot += (e0 + 1) * (th + e1) * pitch * item
+        return tot
+
+    NCH = next((nch for nch in nchs
+                if lds_bytes(TH1, nch) <= LT3_LDS_HARD), None)
+    if NCH is None:
+        return None
+    if env("RAMBA_LT3_SEG"):
+        SEG0 = int(env("RAMBA_LT3_SEG"))
+    else:
+        per = -(-n2 // (NCH * V)) * -(-n1 // TH1)
+        SEG0 = lo = max(4, 4 * max(e[0] for e in fam_ext))
+        for cand in (8, 16, 32, 64):
+            if cand > lo and -(-n0 // cand) * per >= LT3_WORK_MIN:
+                SEG0 = cand
+    return TH1, NCH, SEG0, lds_bytes(TH1, NCH)
+
+
+def generate_load_tiled_3d(plan, fams):
+    """Plane-marching LDS stencil kernel (kind 'lt3') for a 3-D plan and
+    its families from find_stencil_families_3d; None when no tile geometry
+    fits LDS.  Per family the ring is [E0+1][TH1+E1][pitch]; slot = input
+    plane mod (E0+1).  Fill and compute deal (row, 16-byte unit) pairs to
+    the 256 threads flat, so with NCH = 64 lane tx owns unit tx of the rows
+    ty, ty+4, ... and narrower strips keep every lane busy."""
+    fam_members = {}
+    fam_ext = []
+    for fi, (anchor, s0, s1, dt, mem, rep) in enumerate(fams):
+        for (n, d0, d1, d2) in mem:
+            fam_members[n] = (fi, d0, d1, d2)
+        fam_ext.append(tuple(max(m[k] for m in mem) for k in (1, 2, 3)))
+    other_ops = [op for op in plan.operands if op.name not in fam_members]
+    written = {st.target for st in plan.statements}
+    fam_items = [np.dtype(f[3]).itemsize for f in fams]
+    V = max(1, 16 // max(fam_items + [np.dtype(o.dtype).itemsize
+                                      for o in other_ops]))
+    geom = _lt3_geometry(plan.itershape, fam_ext, fam_items, V)
+    if geom is None:
+        return None
+    TH1, NCH, SEG0, _ = geom
+    CW = NCH * V
+
+    key = hashlib.sha256(repr((
+        "loadtiled3d", [(st.target, st.expr) for st in plan.statements],
+        [(fi, f[3], sorted(f[4])) for fi, f in enumerate(fams)],
+        [(o.name, str(o.dtype), o.name in written, o.strides[2] == 1)
+         for o in other_ops],
+        sorted((n, str(dt)) for n, (v, dt) in plan.scalars.items()),
+        sorted((n, str(dt)) for n, dt in plan.dead_vars.items()),
+        TH1, NCH, SEG0, V)).encode()).hexdigest()[:24]
+    kname = f"lt3_{key}"
+
+    A = KernelArgs("Lt3Args")
+    for n in ("n0", "n1", "n2", "gs0", "gs1", "gs2"):
+        A.i64(n)
+    for fi, f in enumerate(fams):
+        A.ptr(ctype(f[3]), f"fam{fi}_ptr")
+        for m in ("off", "s0", "s1"):
+            A.i64(f"fam{fi}_{m}")
+    for o in other_ops:
+        A.view(ctype(o.dtype), o.name, nd=3)
+    for n in sorted(plan.scalars):
+        A.scalar(n, plan.scalars[n][1])
+    L = [PREAMBLE, A.decl()]
+
+    L.append(f'extern "C" __global__ void __launch_bounds__(256) '
+             f"{kname}(Lt3Args a) {{")
+    for fi, (E0, E1, E2) in enumerate(fam_ext):
+        pitch = -(-(CW + E2) // V) * V + V
+        L.append(f"  __shared__ __attribute__((aligned(16))) "
+                 f"{ctype(fams[fi][3])} lds_f{fi}[{E0 + 1}][{TH1 + E1}]"
+                 f"[{pitch}];")
+    L.append(f"  const i64 strips = (a.n2 + {CW} - 1) / {CW};")
+    L.append(f"  const i64 tiles1 = (a.n1 + {TH1} - 1) / {TH1};")
+    L.append(f"  const i64 nseg = (a.n0 + {SEG0} - 1) / {SEG0};")
+    L.append("  for (i64 work = blockIdx.x; work < strips * tiles1 * nseg; "
+             "work += gridDim.x) {")
+    L.append("    const i64 wq = work / strips;")
+    L.append(f"    const i64 k2o = (work % strips) * {CW};")
+    L.append(f"    const i64 k1o = (wq % tiles1) * {TH1};")
+    L.append(f"    const i64 p0 = (wq / tiles1) * {SEG0};")
+    L.append(f"    i64 tmax_ = a.n0 - p0; "
+             f"const int tmax = (int)(tmax_ < {SEG0} ? tmax_ : {SEG0});")
+    for fi in range(len(fams)):
+        L.append(f"    int base{fi} = 0;   // ring slot of input plane k0")
+    L.append("    for (int t = 0; t < tmax; ++t) {")
+    L.append("      const i64 k0 = p0 + t;")
+
+    # ---- fill: the first step loads planes k0 .. k0+E0, later steps the
+    # one new plane k0+E0 over the oldest (k0-1); k0 + E0 <= n0 - 1 + E0,
+    # rows clamp to n1 + E1 and columns to n2 + E2: the views' bounding box
+    for fi, (E0, E1, E2) in enumerate(fam_ext):
+        ct = ctype(fams[fi][3])
+        vct = _LT3_VEC.get((ct, V))
+        ROWS, FW, RING = TH1 + E1, CW + E2, E0 + 1
+        NCHF = -(-FW // V)
+        tail = (f"for (int j = 0; j < {V}; ++j) if (col + j < fw) "
+                f"lds_f{fi}[slot][r][col + j] = a.fam{fi}_ptr[g + j];")
+        L.append(f"      {{ i64 rh_ = a.n1 + {E1} - k1o; "
+                 f"const int rh = (int)(rh_ < {ROWS} ? rh_ : {ROWS});")
+        L.append(f"        i64 fw_ = a.n2 + {E2} - k2o; "
+                 f"const int fw = (int)(fw_ < {FW} ? fw_ : {FW});")
+        L.append(f"        for (int pl = (t == 0 ? 0 : {E0}); pl <= {E0}; "
+                 "++pl) {")
+        L.append(f"          int slot = base{fi} + pl; "
+                 f"if (slot >= {RING}) slot -= {RING};")
+        L.append(f"          const i64 pb = a.fam{fi}_off + (k0 + pl) * "
+                 f"a.fam{fi}_s0 + k1o * a.fam{fi}_s1 + k2o;")
+        L.append(f"          for (int u = threadIdx.x; u < rh * {NCHF}; "
+                 "u += 256) {")
+        L.append(f"            const int r = u / {NCHF}, "
+                 f"col = (u % {NCHF}) * {V};")
+        L.append(f"            const i64 g = pb + r * a.fam{fi}_s1 + col;")
+        if vct:
+            L.append(f"            if (col + {V} <= fw) {{")
+            L.append(f"              {vct} v; __builtin_memcpy(&v, "
+                     f"&a.fam{fi}_ptr[g], sizeof(v));")
+            L.append(f"              __builtin_memcpy(__builtin_assume_aligned"
+                     f"(&lds_f{fi}[slot][r][col], sizeof(v)), &v, "
+                     "sizeof(v));")
+            L.append(f"            }} else {{ {tail} }}")
+        else:
+            L.append(f"            {tail}")
+        L.append("          }")
+        L.append("        } }")
+    L.append("      __syncthreads();")
+
+    # ---- compute one output plane ---------------------------------------
+    def mk_resolver(jexpr):
+        def resolve0(base_name, em):
+            if base_name in fam_members:
+                fi, d0, d1, d2 = fam_members[base_name]
+                return (f"lds_f{fi}[sl{fi}_{d0}][r2 + {d1}]"
+                        f"[cx * {V} + {jexpr} + {d2}]")
+            for o in other_ops:
+                if o.name == base_name:
+                    # a literal unit stride lets the V loads merge
+                    s2 = "" if o.strides[2] == 1 else f" * a.{base_name}_s2"
+                    return (f"a.{base_name}_ptr[a.{base_name}_off + k0 * "
+                            f"a.{base_name}_s0 + k1_t * a.{base_name}_s1 + "
+                            f"(k2_t + {jexpr}){s2}]")
+            return None
+        return resolve0
+
+    def idx(jexpr):
+        return ["(a.gs0 + k0)", "(a.gs1 + k1_t)", f"(a.gs2 + k2_t + {jexpr})"]
+
+    L.append(f"      for (int u = threadIdx.x; u < {TH1 * NCH}; u += 256) {{")
+    L.append(f"        const int r2 = u / {NCH}, cx = u % {NCH};")
+    L.append("        const i64 k1_t = k1o + r2;")
+    L.append(f"        const i64 k2_t = k2o + cx * {V};")
+    L.append("        if (k1_t >= a.n1 || k2_t >= a.n2) continue;")
+    for (fi, d0) in sorted({(m[0], m[1]) for m in fam_members.values()}):
+        RING = fam_ext[fi][0] + 1
+        L.append(f"        int sl{fi}_{d0} = base{fi} + {d0}; "
+                 f"if (sl{fi}_{d0} >= {RING}) sl{fi}_{d0} -= {RING};")
+    L.append(f"        if (k2_t + {V} <= a.n2) {{")
+    store_vecs = {}
+    for j in range(V):
+        genj = _StageGen(plan.statements, mk_resolver(str(j)),
+                         plan.dead_vars)
+        em = LaneEmitter(genj, f"_j{j}", idx(str(j)))
+        finals = genj.emit_into(em)
+        L.extend(em.lines)
+        for o in other_ops:
+            if o.name in written:
+                store_vecs.setdefault(o.name, []).append(finals[o.name])
+    for o in other_ops:
+        if o.name not in written:
+            continue
+        vct = _LT3_VEC.get((ctype(o.dtype), V))
+        vals = store_vecs[o.name]
+        at = (f"a.{o.name}_ptr[a.{o.name}_off + k0 * a.{o.name}_s0 + "
+              f"k1_t * a.{o.name}_s1 + ")
+        if vct and o.strides[2] == 1:
+            L.append(f"        {{ {vct} sv; " + " ".join(
+                f"sv[{j}] = {vals[j]};" for j in range(V)))
+            L.append(f"          __builtin_memcpy(&{at}k2_t], &sv, "
+                     "sizeof(sv)); }")
+        else:
+            for j in range(V):
+                L.append(f"        {at}(k2_t + {j}) * a.{o.name}_s2] = "
+                         f"{vals[j]};")
+    L.append("        } else {")
+    L.append(f"          for (int j = 0; j < {V}; ++j) {{")
+    L.append("            if (k2_t + j >= a.n2) break;")
+    gene = _StageGen(plan.statements, mk_resolver("j"), plan.dead_vars)
+    eme = LaneEmitter(gene, "_je", idx("j"))
+    finals_e = gene.emit_into(eme)
+    L.extend(eme.lines)
+    for o in other_ops:
+        if o.name in written:
+            L.append(f"            a.{o.name}_ptr[a.{o.name}_off + k0 * "
+                     f"a.{o.name}_s0 + k1_t * a.{o.name}_s1 + (k2_t + j) * "
+                     f"a.{o.name}_s2] = {finals_e[o.name]};")
+    L.append("          }")
+    L.append("        }")
+    L.append("      }")
+    L.append("      __syncthreads();")
+    for fi, (E0, E1, E2) in enumerate(fam_ext):
+        L.append(f"      if (++base{fi} > {E0}) base{fi} = 0;")
+    L.append("    }")
+    L.append("  }")
+    L.append("}")
+    return GeneratedKernel(
+        "lt3", key, "\n".join(L), kname, A, tile=(TH1, CW, SEG0),
+        fam_meta=[(rep, anchor, s0, s1)
+                  for (anchor, s0, s1, dt, mem, rep) in fams],
         others=[o.name for o in other_ops])

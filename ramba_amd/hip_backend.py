@@ -553,8 +553,11 @@ class HipBackend:
             gk = self._maybe_load_tiled(plan) or self._get_kernel(plan)
             if recipe is not None:
                 recipe.backend_kernel = gk
-        if gk.kind == "lt":
-            self._launch_load_tiled(gk, plan)
+        if gk.kind in ("lt", "lt3"):
+            if gk.kind == "lt":
+                self._launch_load_tiled(gk, plan)
+            else:
+                self._launch_load_tiled_3d(gk, plan)
             if ntiming:
                 add_time("hb_submit", _time.perf_counter() - _t0)
             return []
@@ -1657,6 +1660,8 @@ class HipBackend:
         # occupancy: 36 KB LDS -> 2.24 ms.)
         if os.environ.get("RAMBA_STENCIL_LDS", "1") == "0":
             return None
+        if len(plan.itershape) == 3:
+            return self._maybe_load_tiled_3d(plan)
         if plan.reductions or len(plan.itershape) != 2:
             return None
         if plan.itershape[0] * plan.itershape[1] < (1 << 16):
@@ -1699,3 +1704,62 @@ class HipBackend:
         gx = max(1, min(int(os.environ.get("RAMBA_GRID_CAP", "32768")),
                         ntiles))
         self._launch(gk, (gx, 1, 1), gk.args.pack(vals), "load_tiled")
+
+    def _maybe_load_tiled_3d(self, plan):
+        """The 3-D arm: a plan of at least RAMBA_LT3_MIN elements with a
+        stencil family runs on the plane-marching LDS kernel (kind 'lt3');
+        None sends it to the vectorized kernel."""
+        if plan.reductions:
+            return None
+        n0, n1, n2 = plan.itershape
+        if n0 * n1 * n2 < int(os.environ.get("RAMBA_LT3_MIN",
+                                             str(codegen.LT3_MIN))):
+            return None
+        fams = codegen.find_stencil_families_3d(plan)
+        if not fams:
+            return None
+        # the tile footprint is the box anchor .. anchor + (n + E - 1) per
+        # axis: it must lie in the family's allocation
+        opmap = {o.name: o for o in plan.operands}
+        for (anchor, s0, s1, dt, mem, rep) in fams:
+            e0, e1, e2 = (max(m[k] for m in mem) for k in (1, 2, 3))
+            last = anchor + (n0 - 1 + e0) * s0 + (n1 - 1 + e1) * s1 \
+                + n2 - 1 + e2
+            if anchor < 0 or last >= self._cont(opmap[rep].bd).numel():
+                return None
+        gk = codegen.generate_load_tiled_3d(plan, fams)
+        if gk is None:
+            return None         # no tile geometry fits LDS
+        cached = self.kernels.get(("lt3", gk.key))
+        if cached is None:
+            cached = self.kernels[("lt3", gk.key)] = self._compile(
+                gk, "load_tiled_3d")
+        gk.handle = cached.handle
+        return gk
+
+    def _launch_load_tiled_3d(self, gk, plan):
+        opmap = {o.name: o for o in plan.operands}
+        vals = {}
+        for d in range(3):
+            vals[f"n{d}"] = plan.itershape[d]
+            vals[f"gs{d}"] = plan.global_start[d]
+        for fi, (rep, anchor, s0, s1) in enumerate(gk.fam_meta):
+            vals[f"fam{fi}_ptr"] = self._cont(opmap[rep].bd).data_ptr()
+            vals[f"fam{fi}_off"] = anchor
+            vals[f"fam{fi}_s0"] = s0
+            vals[f"fam{fi}_s1"] = s1
+        for name in gk.others:
+            op = opmap[name]
+            vals[f"{name}_ptr"] = self._cont(op.bd).data_ptr() \
+                if op.kind == "container" else self.temps[name].data_ptr()
+            vals[f"{name}_off"] = op.offset0
+            for d in range(3):
+                vals[f"{name}_s{d}"] = op.strides[d]
+        for n, (v, dt) in plan.scalars.items():
+            vals[n] = v
+        th, cw, seg = gk.tile
+        n0, n1, n2 = plan.itershape
+        items = -(-n0 // seg) * -(-n1 // th) * -(-n2 // cw)
+        gx = max(1, min(int(os.environ.get("RAMBA_GRID_CAP", "32768")),
+                        items))
+        self._launch(gk, (gx, 1, 1), gk.args.pack(vals), "load_tiled_3d")
